@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: leapfrog steps/sec, many-chain HMC on BASELINE.json config 3.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Workload: ill-conditioned Gaussian, D = 1024, precision
 lam = logspace(0, 4, D); HMC with L = 64 leapfrog steps, eps = 0.006, a streamed
@@ -19,7 +19,20 @@ box with fewer GPUs than ranks they share the visible GPUs and rendezvous over g
 (`"shared_gpu": true`: exercises the N > 1 code path, its numbers are not measurements).
 
 One JSON line is printed by rank 0.  `value` is the weak-scaling figure (65,536 chains per
-GPU); `value_strong` is the same metric with 65,536 chains per NODE (65,536 / N per GPU).
+GPU); `ms_per_step` is the time of one timed step (one draw of every chain).  A plain run does only
+that: it sets up, warms up (`--warmup`), times exactly `--steps` draws, writes the last timed draw's
+outputs when `--dump-outputs DIR` is given, and prints the line.  The other figures -- strong scaling,
+`roofline`, clocks, ESS/sec, `cpu_baseline`, `cfg3_strong_shard`, `fused_builtin`, `secondary` -- are
+measured only with `--full` (each can still be dropped there with its `--no-...` option).
+
+`--dump-outputs DIR` writes what the last timed sample() returned (rank 0's chains): `logp.npy`, the
+log density of every chain [C], and `theta.npy`, the rows [n, D] of a fixed sample of n = 4,096
+chains (numpy default_rng(20241), without replacement, in ascending order: 32 MiB instead of the
+whole 512 MiB state), both float64.  The inputs are seeded, so two builds run with the same
+arguments can be compared output for output.
+
+`value_strong` is the same metric with 65,536 chains per NODE (65,536 / N per GPU; at N = 1 it is
+`value`, at N > 1 it takes a run of its own and is null without `--full`).
 `roofline` is for the dominant kernel (the fused kick+drift, 40*D algorithmic bytes per chain
 per launch), its duration measured live with HIP events on the launch stream over the timed
 region -- around every 8th launch, spread evenly (`roofline.event_stride`): an event record is a
@@ -350,7 +363,8 @@ def device_identity(index):
 
 
 def _device_record(index, clocks):
-    """The `device` object of the line; whatever cannot be read is None (it must never cost the headline)."""
+    """The `device` object of the line; whatever cannot be read is None (it must never cost the headline).  `clocks`:
+    a ClockSampler that ran over the timed region, or None (a plain run samples no clocks)."""
     rec = {"name": None, "identity": None, "clocks": None, "lib_sha256_16": None}
     try:
         import torch
@@ -358,7 +372,8 @@ def _device_record(index, clocks):
         rec["name"] = torch.cuda.get_device_name(index)
     except Exception:
         pass
-    for key, fn in (("identity", lambda: device_identity(index)), ("clocks", clocks.summary), ("lib_sha256_16", lib_hash)):
+    for key, fn in (("identity", lambda: device_identity(index)), ("clocks", clocks.summary if clocks else lambda: None),
+                    ("lib_sha256_16", lib_hash)):
         try:
             rec[key] = fn()
         except Exception:
@@ -682,6 +697,30 @@ class RankContext:
             dist.destroy_process_group()
 
 
+DUMP_ROWS = 4096  # chains whose theta rows --dump-outputs writes (4,096 x 1,024 doubles = 32 MiB)
+
+
+def dump_outputs(path, theta, logp):
+    """Write what one sample() returned -- theta [C, D] and logp [C] on the device -- as .npy files under `path`:
+    logp whole, theta for a fixed sample of DUMP_ROWS chains (seeded, ascending).  Returns the record for the line."""
+    import numpy as np
+    import torch
+
+    C, D = theta.shape
+    rows = np.sort(np.random.default_rng(SEED_CFG3).choice(C, size=min(C, DUMP_ROWS), replace=False))
+    idx = torch.as_tensor(rows, dtype=torch.int64, device=theta.device)
+    arrays = {"theta": theta.index_select(0, idx), "logp": logp}
+    os.makedirs(path, exist_ok=True)
+    files = {}
+    for name, a in arrays.items():
+        a = a.detach().to("cpu", torch.float64).numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        files[name] = list(a.shape)
+    return {"dir": path, "files": files, "dtype": "float64",
+            "theta_rows": f"{len(rows)} of {C} chains: numpy default_rng({SEED_CFG3}).choice(C, {len(rows)}, "
+                          "replace=False), ascending"}
+
+
 # ---------------------------------------------------------------------------------------------
 # one rank
 # ---------------------------------------------------------------------------------------------
@@ -714,7 +753,7 @@ def run_rank(args):
     args.gpus = world
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.only is None:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.only is None:
         cpu = cpu_baseline()  # before the GPU is initialised (worker processes never touch it)
     pinned = pin_rank(local_rank, world)  # before torch / HIP create their threads
 
@@ -749,15 +788,28 @@ def run_rank(args):
 
     for _ in range(args.warmup):
         s.sample()
-    if not args.no_kernel_events:
+    if args.full and not args.no_kernel_events:
         ops.timed = {"bk_leapfrog_kick_drift": [], "bk_target_diag_gaussian_grad": []}
         # every 8th launch of each is bracketed by HIP events (a sample spread evenly over the timed region): an event
         # record is a packet of its own on the queue, and 256 of them per draw cost the draw itself 4 %
         ops.timed_stride = int(os.environ.get("BK_BENCH_EVENT_STRIDE", "8"))
-    with ClockSampler(ctx.local) as clocks:
-        elapsed = ctx.timed_loop(s.sample, args.steps)
+    step, last, calls = s.sample, [], [0]
+    if args.dump_outputs:
+        def step():  # keeps what the LAST timed draw returned; earlier returns are dropped, as the plain loop drops them
+            out = s.sample()
+            calls[0] += 1
+            if calls[0] == args.steps:
+                last.append(out)
+    clocks = ClockSampler(ctx.local) if args.full else None
+    if clocks:
+        with clocks:
+            elapsed = ctx.timed_loop(step, args.steps)
+    else:
+        elapsed = ctx.timed_loop(step, args.steps)
     timed, ops.timed = ops.timed, None
     event_stride, ops.timed_stride = ops.timed_stride, 1
+    dumped = dump_outputs(args.dump_outputs, *last[-1]) if args.dump_outputs and rank == 0 else None
+    del last
     accept = s.accept_rate()
 
     # an N > 1 run is a measurement only if every rank is really in the RCCL group: an all_reduce of ones that completed
@@ -853,7 +905,9 @@ def run_rank(args):
             out["roofline"]["device_copy_GBps"] = 10 * 2.0 * src.numel() * 8 / (e0.elapsed_time(e1) * 1e-3) / 1e9
         except Exception:  # context only
             out["roofline"]["device_copy_GBps"] = None
-    if args.ess_draws > 0:
+    if dumped is not None:
+        out["dump_outputs"] = dumped
+    if args.full and args.ess_draws > 0:
         try:
             # Second half of BASELINE.json's metric: ESS/sec.  Extra draws (outside the timed region
             # above), three tracked coordinates + the returned log density, ESS by the reference's
@@ -897,7 +951,7 @@ def run_rank(args):
     # Strong scaling: the same metric with 65,536 chains per NODE (65,536 / N per GPU).  At N = 1 it
     # is the headline run itself.  At N = 8 each GPU holds 8,192 chains = 64 MiB arrays, which live
     # in the Infinity Cache: a different regime from the HBM-bound weak figure, reported beside it.
-    if world == 1 or args.no_strong:
+    if world == 1 or args.no_strong or not args.full:
         out["value_strong"] = value if world == 1 else None
     else:
         try:
@@ -916,9 +970,9 @@ def run_rank(args):
             out["value_strong"] = None
             out["strong"] = {"error": repr(e)}
 
-    if world == 1 and not args.no_strong_shard:
+    if args.full and world == 1 and not args.no_strong_shard:
         out["cfg3_strong_shard"] = strong_shard_entries(ctx, args, value)
-    if not args.no_fused_extra:
+    if args.full and not args.no_fused_extra:
         try:
             # Separately reported (never priced on the 56*D model): the same workload through the
             # built-in target's register-resident whole-draw kernel (bk_hmc_draw_gaussian: trajectory
@@ -969,7 +1023,7 @@ def run_rank(args):
         except Exception as e:  # the extra must never cost the headline line
             ops.timed = None
             out["fused_builtin"] = {"error": repr(e)}
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         # N = 1: every other BASELINE.json config.  N > 1: config 4, the one north_star shards with a
         # cross-rank reduction (32,768 chains per rank, R-hat / ESS over the process group).
         from bench_secondary import run_secondary
@@ -991,6 +1045,13 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--chains", type=int, default=None, help="chains per GPU (default: 65,536)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: kernel events and roofline, clocks, ESS/sec, "
+                         "CPU baseline, strong scaling, the fused draw and the other configs (the --no-... options "
+                         "drop parts of it); a plain run sets up, warms up, times --steps draws and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed draws, write what the last one returned as DIR/theta.npy (rows of a fixed "
+                         f"sample of {DUMP_ROWS} chains) and DIR/logp.npy (every chain), float64 (rank 0)")
     ap.add_argument("--only", choices=["cfg2", "cfg4", "mala", "torch_model", "cfg5"], default=None,
                     help="run ONE secondary workload alone and print its record (profiling runs)")
     ap.add_argument("--chain-tile", type=int, default=None,
@@ -1011,6 +1072,10 @@ def parse_args(argv=None):
                     help="skip config 3 at the per-rank shard sizes of the metric (8,192 / 16,384 / 32,768 chains; N=1 only)")
     ap.add_argument("--ess-draws", type=int, default=200, help="extra draws for the ESS/sec figure (0 = skip)")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.only is not None:
+        ap.error("--dump-outputs writes the headline's outputs; it does not apply to --only")
     args.steps_given = any(a == "--steps" or a.startswith("--steps=") for a in (sys.argv[1:] if argv is None else argv))
     return args
 

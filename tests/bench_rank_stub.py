@@ -18,8 +18,14 @@ if sys.argv[1] == "fail1" and rank == 1:
 if sys.argv[1] == "cfg4":
     ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
     sys.path[:0] = [ROOT, os.path.join(ROOT, "bayes-kit_amd")]
+    import functools
+
     import bench
 
+    # the CPU stand-in of GPU ranks: whatever GPUs the box running the test has are not theirs, so they are placed as on a
+    # box without a readable GPU topology (the NUMA path is covered by test_rank_cpu_sets_follow_the_numa_node_of_the_gpu)
+    bench._gpu_numa_node = lambda index: None
+    bench.rank_cpu_set = functools.partial(bench.rank_cpu_set, numa_of_gpu=bench._gpu_numa_node)
     pinned = bench.pin_rank(rank, world)  # (as a bench rank does, before the process group exists)
 dist.init_process_group("gloo", rank=rank, world_size=world)
 dist.barrier()

@@ -1,8 +1,10 @@
 """Shared test helpers: load golden cases and rebuild their oracle-side objects."""
 import json
 import os
+import pathlib
 
 import numpy as np
+import pytest
 
 from oracle import models as omodels
 from oracle import samplers as osamplers
@@ -149,3 +151,46 @@ def smc_model(spec):
 def smc_expected_thetas(z):
     """The particles after every resampling: moved[n][idx[n]] (the generator checked this against the reference)."""
     return np.stack([z["moved"][n][z["idx"][n]] for n in range(z["idx"].shape[0])])
+
+
+@pytest.fixture()
+def cache_tmp_path(tmp_path):
+    """A scratch directory for CTarget.from_source caches.  The library refuses to load code from below a directory that
+    belongs to another user (targets._check_ancestors), and pytest's tmp_path can lie below one (a temporary root inside a
+    home directory that is somebody else's).  Then a fresh private directory under a system temporary root that passes the
+    check serves instead, and is removed afterwards."""
+    import shutil
+    import tempfile
+
+    from bayes_kit_amd import _lib, targets
+
+    def trusted(d):
+        try:
+            targets._check_ancestors(os.path.join(str(d), "cache"))
+            return True
+        except _lib.BkHipError:
+            return False
+
+    if trusted(tmp_path):
+        yield tmp_path
+        return
+    for root in ("/tmp", "/var/tmp", "/dev/shm"):
+        try:
+            d = tempfile.mkdtemp(prefix="bk_test_", dir=root)
+        except OSError:
+            continue
+        if trusted(d):
+            break
+        shutil.rmtree(d, ignore_errors=True)
+    else:
+        pytest.fail(f"no temporary directory below which CTarget.from_source trusts a cache (tmp_path: {tmp_path})")
+    try:
+        yield pathlib.Path(d)
+    finally:
+        for dirpath, dirnames, _ in os.walk(d):  # (tests chmod what they made; make all of it removable again)
+            for n in dirnames:
+                try:
+                    os.chmod(os.path.join(dirpath, n), 0o700)
+                except OSError:
+                    pass
+        shutil.rmtree(d, ignore_errors=True)

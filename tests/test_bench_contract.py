@@ -11,7 +11,7 @@ def test_cli_help_and_defaults():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True,
                          timeout=120)
     assert out.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--only"):
+    for flag in ("--gpus", "--steps", "--warmup", "--only", "--full", "--dump-outputs"):
         assert flag in out.stdout
 
 
@@ -152,7 +152,9 @@ def test_eight_ranks_on_the_cpu_stand_in_reduce_rhat_over_all_chains_and_get_the
 
     stub = [sys.executable, os.path.join(ROOT, "tests", "bench_rank_stub.py")]
     buf = io.StringIO()
-    rc = bench.launch_ranks(8, stub + ["cfg4"], {"OMP_NUM_THREADS": "1"}, timeout=600, out=buf)
+    # (no GPU visibility mask: with one, pin_rank leaves the affinity alone, and the stand-in ranks use no GPU)
+    unmask = {v: "" for v in ("HIP_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES", "ROCR_VISIBLE_DEVICES") if v in os.environ}
+    rc = bench.launch_ranks(8, stub + ["cfg4"], {"OMP_NUM_THREADS": "1", **unmask}, timeout=600, out=buf)
     assert rc == 0
     r = json.loads(buf.getvalue().strip().splitlines()[-1])
     assert r["n_gpus"] == 8 and r["rhat_over_chains"] == 8 * 6 and r["chain_id0"] == [6 * k for k in range(8)]
@@ -178,3 +180,31 @@ def test_rank_cpu_sets_follow_the_numa_node_of_the_gpu():
     assert bench.rank_cpu_set(0, 1, affinity={3, 4}) == {3, 4}
     # more ranks than CPUs: ranks share, nobody gets an empty set
     assert all(bench.rank_cpu_set(r, 8, affinity={0, 1}, numa_of_gpu=lambda i: None) for r in range(8))
+
+
+def test_plain_run_options_and_the_output_dump(tmp_path):
+    """A plain run is the headline alone (--full adds the rest); --dump-outputs writes what the last timed sample()
+    returned: logp whole, theta rows of a fixed seeded sample of chains, float64, within 64 MB at the benchmark's shape."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import pytest
+    import torch
+
+    import bench
+
+    a = bench.parse_args(["--steps", "7", "--warmup", "1"])
+    assert a.steps == 7 and a.warmup == 1 and not a.full and a.dump_outputs is None
+    assert bench.parse_args(["--full", "--dump-outputs", str(tmp_path)]).full
+    for bad in (["--steps", "0"], ["--warmup", "-1"], ["--only", "cfg4", "--dump-outputs", str(tmp_path)]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+    C, D = 5000, 8
+    theta = torch.arange(C * D, dtype=torch.float64).reshape(D, C).t()   # a [C, D] view of a [D, C] array, as sample() returns
+    logp = torch.linspace(-3.0, 1.0, C, dtype=torch.float64)
+    rec = bench.dump_outputs(str(tmp_path / "out"), theta, logp)
+    th, lp = np.load(tmp_path / "out" / "theta.npy"), np.load(tmp_path / "out" / "logp.npy")
+    rows = np.sort(np.random.default_rng(bench.SEED_CFG3).choice(C, bench.DUMP_ROWS, replace=False))
+    assert th.dtype == np.float64 and lp.dtype == np.float64 and rec["files"] == {"theta": [bench.DUMP_ROWS, D], "logp": [C]}
+    assert np.array_equal(th, theta.numpy()[rows]) and np.array_equal(lp, logp.numpy())
+    assert sorted(os.listdir(tmp_path / "out")) == ["logp.npy", "theta.npy"]
+    assert (bench.DUMP_ROWS * bench.D_CFG3 + bench.C_CFG3) * 8 <= 64e6

@@ -9,6 +9,7 @@ import pytest
 
 import bayes_kit_amd as bk
 from bayes_kit_amd import targets as T
+from tests.helpers import cache_tmp_path  # noqa: F401  (fixture)
 
 TERM = """
 __device__ void bk_term(double th, i64 d, const double* lam, double& term, double& grad) {
@@ -35,8 +36,8 @@ template <class L> __device__ double bk_lanes_density(L& c, const double*) {
 
 
 @pytest.fixture()
-def cache(tmp_path, monkeypatch):
-    d = tmp_path / "cache"
+def cache(cache_tmp_path, monkeypatch):
+    d = cache_tmp_path / "cache"
     monkeypatch.setenv("BK_SOURCE_TARGET_DIR", str(d))
     return d
 
@@ -133,16 +134,16 @@ def test_cached_library_others_can_write_or_own_is_refused(cache):
         os.chown(cache, 0, -1)
 
 
-def test_default_cache_is_private_and_per_user(tmp_path, monkeypatch):
+def test_default_cache_is_private_and_per_user(cache_tmp_path, monkeypatch):
     monkeypatch.delenv("BK_SOURCE_TARGET_DIR", raising=False)
-    monkeypatch.setenv("XDG_CACHE_HOME", str(tmp_path / "xdg"))
+    monkeypatch.setenv("XDG_CACHE_HOME", str(cache_tmp_path / "xdg"))
     d = T._source_cache_dir()
-    assert d == str(tmp_path / "xdg" / "bayes_kit_amd") and stat.S_IMODE(os.lstat(d).st_mode) == 0o700
+    assert d == str(cache_tmp_path / "xdg" / "bayes_kit_amd") and stat.S_IMODE(os.lstat(d).st_mode) == 0o700
     monkeypatch.delenv("XDG_CACHE_HOME")
-    monkeypatch.setenv("HOME", str(tmp_path / "home"))
-    assert T._source_cache_dir() == str(tmp_path / "home" / ".cache" / "bayes_kit_amd")
+    monkeypatch.setenv("HOME", str(cache_tmp_path / "home"))
+    assert T._source_cache_dir() == str(cache_tmp_path / "home" / ".cache" / "bayes_kit_amd")
     # no usable home: a fresh mkdtemp directory (0700, unpredictable name), never a fixed path under /tmp
-    ro = tmp_path / "ro"
+    ro = cache_tmp_path / "ro"
     ro.mkdir()
     (ro / "file").write_text("")
     monkeypatch.setenv("XDG_CACHE_HOME", str(ro / "file"))  # makedirs under a FILE fails for every uid, root included
@@ -236,10 +237,10 @@ def test_prewarm_builds_a_list_of_sources_in_parallel_and_records_what_was_asked
     assert len(manifest) > 40 and all({"user_source", "form", "dims"} <= set(m) for m in manifest)
 
 
-def test_cache_below_a_directory_others_can_write_is_refused(tmp_path, monkeypatch):
+def test_cache_below_a_directory_others_can_write_is_refused(cache_tmp_path, monkeypatch):
     """a leaf that is private is not enough -- a group / world-writable directory ABOVE the cache (without the sticky
     bit) lets somebody else swap the cache directory itself.  A sticky one (/tmp-like) is fine: the leaf is ours."""
-    loose = tmp_path / "shared"
+    loose = cache_tmp_path / "shared"
     loose.mkdir()
     os.chmod(loose, 0o777)
     monkeypatch.setenv("BK_SOURCE_TARGET_DIR", str(loose / "cache"))
@@ -251,9 +252,9 @@ def test_cache_below_a_directory_others_can_write_is_refused(tmp_path, monkeypat
     assert T._source_cache_dir() == str(loose / "cache")
 
 
-def test_default_cache_below_a_loose_directory_falls_back_to_a_private_temporary_one(tmp_path, monkeypatch):
+def test_default_cache_below_a_loose_directory_falls_back_to_a_private_temporary_one(cache_tmp_path, monkeypatch):
     """The DEFAULT location ($XDG_CACHE_HOME) below a world-writable directory: not trusted, but not fatal either."""
-    loose = tmp_path / "xdg"
+    loose = cache_tmp_path / "xdg"
     loose.mkdir()
     os.chmod(loose, 0o777)
     monkeypatch.delenv("BK_SOURCE_TARGET_DIR", raising=False)

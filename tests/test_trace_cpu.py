@@ -11,6 +11,7 @@ import torch
 
 import bayes_kit_amd as bk
 from bayes_kit_amd import trace
+from tests.helpers import cache_tmp_path  # noqa: F401  (fixture)
 
 F = torch.nn.functional
 _BKHIP_MATH_H = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "bkhip_math.h")   # bk_exp
@@ -167,11 +168,13 @@ def test_torch_model_compile_keeps_autograd_when_the_source_cannot_be_built(tmp_
     assert torch.allclose(g, -(Th * lam)) and lp.shape == (3,)
 
 
-def test_torch_model_compile_flag_on_the_build_box(tmp_path, monkeypatch):
+def test_torch_model_compile_flag_on_the_build_box(cache_tmp_path, monkeypatch):
     """compile=True: a traceable function becomes a compiled target (hipcc cross-compiles here; no compute without a GPU);
     an untraceable one warns, names the node, and stays an autograd model."""
-    monkeypatch.setenv("BK_SOURCE_TARGET_DIR", str(tmp_path / "cache"))
-    m = bk.TorchModel(lambda Th: -0.5 * (Th * Th * lam).sum(dim=1), D, compile=True)
+    monkeypatch.setenv("BK_SOURCE_TARGET_DIR", str(cache_tmp_path / "cache"))
+    # (on a box with a GPU the compiled source is checked against the function there: its constant lives on that device)
+    lam_here = lam.to("cuda") if torch.cuda.is_available() else lam
+    m = bk.TorchModel(lambda Th: -0.5 * (Th * Th * lam_here).sum(dim=1), D, compile=True)
     assert m.compiled is not None and m.compile_note is None and "bk_term" in m.traced_source
     assert m.bk_counted and hasattr(m, "bk_eval") and hasattr(m, "bk_hmc_draw") and hasattr(m, "bk_hmc_trajectory")
     assert os.path.exists(m.compiled.source_library)
@@ -314,8 +317,8 @@ def test_lanes_unsupported_shapes_name_the_reason(fn, needle):
         trace_lanes.lanes_source(fn, DL)
 
 
-def test_torch_model_compiles_a_hierarchical_density_into_the_lanes_form(tmp_path, monkeypatch):
-    monkeypatch.setenv("BK_SOURCE_TARGET_DIR", str(tmp_path / "cache"))
+def test_torch_model_compiles_a_hierarchical_density_into_the_lanes_form(cache_tmp_path, monkeypatch):
+    monkeypatch.setenv("BK_SOURCE_TARGET_DIR", str(cache_tmp_path / "cache"))
     m = bk.TorchModel(t_funnel, DL, compile=True)
     assert m.compiled is not None and m.compiled_form == "lanes" and "bk_lanes_density" in m.traced_source
     for hook in ("bk_eval", "bk_leapfrog_step", "bk_hmc_proposal", "bk_dr_proposal"):
@@ -421,8 +424,8 @@ def test_chain_unsupported_shapes_name_the_reason(fn, needle):
         trace_chain.chain_source(fn, DC)
 
 
-def test_torch_model_compiles_a_coupled_density_into_the_per_chain_form(tmp_path, monkeypatch):
-    monkeypatch.setenv("BK_SOURCE_TARGET_DIR", str(tmp_path / "cache"))
+def test_torch_model_compiles_a_coupled_density_into_the_per_chain_form(cache_tmp_path, monkeypatch):
+    monkeypatch.setenv("BK_SOURCE_TARGET_DIR", str(cache_tmp_path / "cache"))
     m = bk.TorchModel(c_ar1, DC, compile=True)
     assert m.compiled is not None and m.compiled_form == "chain" and "bk_chain" in m.traced_source, m.compile_note
     for hook in ("bk_eval", "bk_leapfrog_step", "bk_leapfrog_trajectory"):
