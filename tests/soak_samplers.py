@@ -3,8 +3,8 @@
 Random algorithm (HMC / MALA / DRGHMC / Metropolis), target (iso / diag Gaussian / AR(1)), model provider
 (library target, PyTorch autograd, user code returning a row-major or strided gradient, compiled plugin),
 dims (1..70: both generator kernels), chains (odd and even: scalar and 16-byte kernels), step sizes, trajectory lengths,
-metric on/off, fused / step-by-step, hipGraph on/off, RNG prefetch on/off.  For a few watched chains
-theta must be bit-identical to the oracle at every draw and the stream state equal at the end.
+metric on/off, fused / one launch per step / model-opaque, hipGraph on/off, RNG prefetch on/off.  For a few watched
+chains theta must be bit-identical to the oracle at every draw and the stream state equal at the end.
 SECONDS env var = duration (default 60); SEED = rng seed."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -52,6 +52,7 @@ class Sentinels:
 
 
 PROVIDERS_SEEN = {}
+HMC_PATHS_SEEN = {}  # HMC's path= ("opaque": the gradient a separate op per leapfrog step, as bench.py runs it)
 HISTORY = []  # the last few configurations: a corrupted sampler is usually the victim of an earlier one
 
 
@@ -305,9 +306,10 @@ def one(rng, it):
     del HISTORY[:-8]
     if alg == "hmc":
         L = int(rng.integers(0, 7))
-        kw = dict(path=("step", "auto")[int(rng.integers(0, 2))], graph=bool(rng.integers(0, 2)) and not NO_GRAPH,
-                  prefetch_rng=bool(rng.integers(0, 2)) and not NO_PREFETCH)
+        kw = dict(path=("step", "auto", "opaque")[int(rng.integers(0, 3))],
+                  graph=bool(rng.integers(0, 2)) and not NO_GRAPH, prefetch_rng=bool(rng.integers(0, 2)) and not NO_PREFETCH)
         desc.update(L=L, **kw)
+        HMC_PATHS_SEEN[kw["path"]] = HMC_PATHS_SEEN.get(kw["path"], 0) + 1
         s = bk.HMCDiag(tgt, eps, L, metric_diag=metric, chains=C, seed=seed, **kw)
         mk = lambda sd: osamp.HMCDiag(otgt(), eps, L, metric_diag=metric, seed=sd)
     elif alg == "mala":

@@ -31,20 +31,34 @@ def test_many_chain_vs_reference_golden(name, ops):
     check_many_chain(name, ops)
 
 
-@pytest.mark.parametrize("name", [n for n in MANY if n.startswith("drghmc")])
-def test_drghmc_model_opaque_device_counts_vs_reference_golden(name, ops):
+def _with_opaque(names):
+    """(name, path) pairs over path in {"step", "opaque"}; the "step" cases keep their ids of old (the bare name)."""
+    return pytest.mark.parametrize("name,path", [(n, "step") for n in names] + [(n, "opaque") for n in names],
+                                   ids=list(names) + [n + "-opaque" for n in names])
+
+
+@_with_opaque([n for n in MANY if n.startswith("drghmc")])
+def test_drghmc_model_opaque_device_counts_vs_reference_golden(name, ops, path):
     """The reference's DRGHMC fixtures through the model-opaque path with lane counts on the device: one counted
-    gradient op + one counted kick+drift launch per leapfrog step (drghmc.py:280-283), no host read, one hipGraph."""
-    s = check_many_chain(name, ops, path="step", device_counts=True)
+    gradient op + one counted kick+drift launch per leapfrog step (drghmc.py:280-283), no host read, one hipGraph.
+    path="opaque" also keeps a model's one-launch leapfrog step (bk_leapfrog_step) out of it."""
+    s = check_many_chain(name, ops, path=path, device_counts=True)
     assert s._dev_counts and not s._one_launch and s._use_graph and s.host_syncs_per_draw == 0
+    if path == "opaque":
+        assert not s._step_hook
 
 
-@pytest.mark.parametrize("name", [n for n in MANY if n.startswith("hmc")])
-def test_hmc_step_by_step_path_vs_reference_golden(name, ops):
-    """The model-opaque path (one kick+drift launch and one gradient op per leapfrog step),
-    which is what bench.py measures; the default for built-in Gaussians is the fused one."""
-    s = check_many_chain(name, ops, path="step")
+@_with_opaque([n for n in MANY if n.startswith("hmc")])
+def test_hmc_step_by_step_path_vs_reference_golden(name, ops, path):
+    """The HMC fixtures step by step instead of the default whole-trajectory kernels.  path="step": one launch per
+    leapfrog step ({gradient, kick, drift}: the built-in Gaussians' bk_leapfrog_step hook).  path="opaque": one
+    kick+drift launch and one SEPARATE gradient op per leapfrog step -- what bench.py measures (make_cfg3_sampler)."""
+    s = check_many_chain(name, ops, path=path)
     assert not s._fused
+    if path == "opaque":
+        assert not (s._fused_draw or s._step_hook or s._traj_hook or s._lanes_traj)
+    else:
+        assert s._step_hook
 
 
 @pytest.mark.parametrize("name", ["hmc_pcg_seed", "hmc_iso4", "mala_stdnormal", "mala_init",
@@ -172,10 +186,13 @@ def test_full_size_cfg3_properties(ops):
 
 
 def test_drghmc_many_chains_match_oracle_per_chain(ops):
-    """2,048 funnel chains in lockstep (compaction, ghost levels) vs the oracle chain by chain
-    on a scattered subset: decisions, theta and the RNG position all agree."""
+    """2,048 funnel chains in lockstep (compaction, ghost levels) vs the oracle chain by chain on a scattered subset,
+    the oracle summing in the library's canonical order with the library's exp (oracle.models.FunnelCanonical):
+    theta and the final momentum bit-identical, logp to 1e-12, the RNG position exact."""
     from oracle import models as om
     from oracle import samplers as osamp
+    from tests.helpers import rng_state_words
+    from tests.sampler_parity import LOGP_RTOL
 
     D, C, seed, N = 11, 2048, 909, 12
     args = (3, [0.2, 0.05, 0.0125], [10, 40, 160], 0.1)
@@ -188,15 +205,15 @@ def test_drghmc_many_chains_match_oracle_per_chain(ops):
         stages.update(t for t, _ in s.last_stage_lanes)
     assert {"P0", "P1", "G0(P1)"} <= stages
     st = s.rng_state()
+    rho = s._rho.cpu().numpy()
     for c in list(range(0, C, 97)) + [C - 1]:
-        o = osamp.DrGhmcDiag(om.Funnel(D), *args, seed=np.random.Philox(key=[seed, c]))
+        o = osamp.DrGhmcDiag(om.FunnelCanonical(D), *args, seed=np.random.Philox(key=[seed, c]))
         for n in range(N):
             oth, olp = o.sample()
-            np.testing.assert_allclose(draws[n][0][c], oth, **funnel_tol(n))  # 1e-9: N < 20 draws
-            np.testing.assert_allclose(draws[n][1][c], olp, **funnel_tol(n))
-        from tests.helpers import rng_state_words
-
+            assert np.array_equal(draws[n][0][c], oth), (c, n, float(np.abs(draws[n][0][c] - oth).max()))
+            np.testing.assert_allclose(draws[n][1][c], olp, rtol=LOGP_RTOL, atol=1e-12, err_msg=f"chain {c} draw {n}")
         np.testing.assert_array_equal(st[:, c], rng_state_words(o._rng))
+        assert np.array_equal(rho[c], o._rho), c
 
 
 def test_drghmc_moments_std_normal(ops):
@@ -362,18 +379,21 @@ def test_tempered_smc_binomial_moments(ops):
     check_smc_binomial(ops, 8192, 10, bk.mala_kernel(0.2, 2), mean_atol=0.006, var_atol=0.0012)
 
 
-@pytest.mark.parametrize("path", ["one_launch", "counted_steps"])
+@pytest.mark.parametrize("path", ["one_launch", "counted_steps", "opaque"])
 @pytest.mark.parametrize("name", ["drghmc_funnel11_k3", "drghmc_funnel101_cfg4", "drghmc_funnel17_k4",
                                   "drghmc_funnel33_k2_metric_noretry", "drghmc_funnel129_k3", "drghmc_funnel130_k2"])
 def test_funnel_fixtures_bit_identical_to_the_canonical_order_oracle(ops, name, path):
     """SURVEY 8c's funnel bar is theta rel 1e-9 over <= 50 draws.  HIP against the oracle that sums in the library's
     canonical order and uses the library's exp (the same rounded operations on both sides): theta and momentum
     BIT-IDENTICAL over all draws of every funnel fixture, decisions and stream state exact -- through the one-launch
-    proposal kernel and through counted leapfrog steps."""
+    proposal kernel, through counted leapfrog steps and through the model-opaque path (path="opaque": the gradient a
+    separate op per leapfrog step)."""
     from tests.sampler_parity import check_funnel_vs_canonical_oracle
 
-    extra = {} if path == "one_launch" else dict(path="step")
-    check_funnel_vs_canonical_oracle(name, ops, **extra)
+    extra = {"one_launch": {}, "counted_steps": dict(path="step"), "opaque": dict(path="opaque")}[path]
+    s = check_funnel_vs_canonical_oracle(name, ops, **extra)
+    if path == "opaque":
+        assert not (s._fused or s._one_launch or s._step_hook or s._traj_hook)
 
 
 @pytest.mark.parametrize("source", ["np.random", "RandomState", "replay"])
@@ -660,7 +680,7 @@ def test_reference_test_behaviours_on_device(ops):
     db.check_smc_with_reference_style_model(ops)
 
 
-@pytest.mark.parametrize("alg", ["hmc", "mala", "drghmc"])
+@pytest.mark.parametrize("alg", ["hmc", "hmc_opaque", "mala", "drghmc"])
 def test_long_run_stays_bit_identical_to_the_oracle(ops, alg):
     """4000 draws x 40 dims per chain = 160,000+ normals per stream (tens of ziggurat tail and
     thousands of wedge draws per chain, 40,000 Philox buffer wraps, the wavefront-per-chain
@@ -671,8 +691,9 @@ def test_long_run_stays_bit_identical_to_the_oracle(ops, alg):
 
     C, D, N, seed = 96, 40, 4000, 8675309
     lam = np.logspace(0, 0.7, D)
-    if alg == "hmc":
-        s = bk.HMCDiag(bk.DiagGaussian(lam), 0.2, 3, chains=C, seed=seed, path="step")
+    if alg in ("hmc", "hmc_opaque"):
+        s = bk.HMCDiag(bk.DiagGaussian(lam), 0.2, 3, chains=C, seed=seed, path="step" if alg == "hmc" else "opaque")
+        assert s._step_hook == (alg == "hmc") and not s._fused
         mk = lambda sd: osamp.HMCDiag(om.DiagGaussian(lam), 0.2, 3, seed=sd)  # noqa: E731
     elif alg == "mala":
         s = bk.MALA(bk.DiagGaussian(lam), 0.05, chains=C, seed=seed)
@@ -714,6 +735,7 @@ def test_randomised_sampler_configurations_against_the_oracle(ops):
         seen.add(str(mod.one(rng, it)))
     assert seen == {"hmc", "mala", "drghmc", "metropolis", "drfunnel", "hmcfunnel"}
     assert set(mod.PROVIDERS_SEEN) == {"builtin", "torch", "row", "strided", "plugin"}, mod.PROVIDERS_SEEN
+    assert set(mod.HMC_PATHS_SEEN) == {"step", "auto", "opaque"}, mod.HMC_PATHS_SEEN
 
 
 def test_plain_c_host_program_equals_the_python_driver(ops):

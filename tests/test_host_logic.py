@@ -36,6 +36,14 @@ def test_many_chain_driver_vs_golden_step_by_step(name):
     assert not s._fused
 
 
+@pytest.mark.parametrize("name", [n for n in MANY if n.startswith("hmc")])
+def test_many_chain_driver_vs_golden_model_opaque(name):
+    """path="opaque" (bench.py's headline path): one kick+drift and one separate gradient op per leapfrog step, none of
+    the fused or one-launch hooks a built-in Gaussian offers."""
+    s = check_many_chain(name, FakeOps(), path="opaque")
+    assert not (s._fused or s._fused_draw or s._step_hook or s._traj_hook or s._lanes_traj)
+
+
 @pytest.mark.parametrize("name", SINGLE)
 def test_single_chain_drop_in_vs_golden(name):
     check_single_chain_host_model(name, FakeOps(), chains=[0, 1])
