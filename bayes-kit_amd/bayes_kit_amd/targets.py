@@ -355,6 +355,8 @@ _SRC_USER_COMMENT = {
     "chain": '// ---- user code: ONE CHAIN per call ----------------------------------------------------------------------------------\n//   __device__ double bk_chain(const BkTheta& th, const BkGrad& g, i64 D, const double* params)\n//   returns the log density; writes the gradient with g.set(d, value) (a no-op when none is wanted)\n',
 }
 _SRC_RULE = "// " + "-" * 115 + "\n"
+_SRC_NEIGHBOUR_COMMENT = ("//   neighbour=True: also c.sum_pair(f) with f(double xp, double x, i64 d), xp = theta_{d-1} (0.0 for d == head), and c.grad_pair(f)\n"
+                          "//   with f(...) -> bk_pair{dxp, dx}; g_d = dx(d) + dxp(d+1) (bk_lanes.hpp)\n")
 
 _LANES_MAX_ROWS = 128  # bk_lanes.hpp MAX_ROWS: spread rows a trajectory kernel keeps in registers
 _LANES_MAX_HEAD = 8
@@ -489,7 +491,9 @@ def _find_hipcc():
                           "compiled yourself.")
 
 
-def _source_text(user_source: str, form: str, dims: int, head: int, stage: str = "auto") -> str:
+def _source_text(user_source: str, form: str, dims: int, head: int, stage: str = "auto", neighbour: bool = False) -> str:
+    if neighbour and form != "lanes":
+        raise ValueError("neighbour=True applies to form='lanes' only (rows coupled to row d - 1: c.sum_pair / c.grad_pair)")
     if form not in ("elementwise", "chain", "lanes"):
         raise ValueError("form must be 'elementwise' (bk_term: one coordinate's term and derivative), 'chain' "
                          "(bk_chain: one chain's log density and gradient, one lane per chain) or 'lanes' "
@@ -519,31 +523,37 @@ def _source_text(user_source: str, form: str, dims: int, head: int, stage: str =
         else:
             shape = {"DIMS": int(dims), "STAGE": int(dims) if int(dims) <= 128 else 0,
                      "LDS": int(dims) if 128 < int(dims) <= 300 else 0}
+    if neighbour:   # (only then: the text of every other source stays what it was, and so does its cache key)
+        shape["NEIGHBOUR"] = 1
     defines = "".join(f"#define BK_SOURCE_{k} {v}\n" for k, v in shape.items())
     return (f"// Generated by bayes_kit_amd.CTarget.from_source(form=\"{form}\"): plugin ABI bk_target_fn / bk_target_fn_n "
             "(include/bkhip.h) + the entry points of include/bkhip_source.h.\n"
             f"#define BK_SOURCE_FORM_{form} 1\n" + defines + "#include \"bk_source_api.hpp\"\n"
-            + _SRC_USER_COMMENT[form] + user_source.rstrip("\n") + "\n" + _SRC_RULE + "#include \"bk_source_kernels.hpp\"\n")
+            + _SRC_USER_COMMENT[form] + (_SRC_NEIGHBOUR_COMMENT if neighbour else "")
+            + user_source.rstrip("\n") + "\n" + _SRC_RULE + "#include \"bk_source_kernels.hpp\"\n")
 
 
 _SRC_REQUIRED_EXPORTS = ("bk_src_target", "bk_src_target_n")
 
 
-def _compile_source_target(user_source: str, form: str, contract: bool, dims: int = 1, head: int = 0, stage: str = "auto") -> str:
+def _compile_source_target(user_source: str, form: str, contract: bool, dims: int = 1, head: int = 0, stage: str = "auto",
+                           neighbour: bool = False) -> str:
     """hipcc the generated translation unit into a shared library (cached by content: the generated text, the flags and the
     library headers it includes); returns its path."""
     import hashlib
     import os
     import subprocess
 
-    text = _source_text(user_source, form, int(dims), int(head), stage)
+    text = _source_text(user_source, form, int(dims), int(head), stage, bool(neighbour))
     rec = os.environ.get("BK_SOURCE_RECORD")
     if rec:   # (a log of what was asked for, one JSON object per line: `prewarm_sources` builds such a list in parallel)
         import json
 
+        spec = dict(user_source=user_source, form=form, contract=bool(contract), dims=int(dims), head=int(head), stage=stage)
+        if neighbour:
+            spec["neighbour"] = True
         with open(rec, "a") as f:
-            f.write(json.dumps(dict(user_source=user_source, form=form, contract=bool(contract), dims=int(dims),
-                                    head=int(head), stage=stage)) + "\n")
+            f.write(json.dumps(spec) + "\n")
     csrc = _csrc_dir()
     inc = os.path.abspath(os.path.join(csrc, "..", "..", "include"))
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fno-fast-math",
@@ -603,7 +613,7 @@ def prewarm_sources(specs, workers=None, errors=None):
     """Build the libraries of many from_source densities AHEAD, in parallel (one hipcc each, `workers` at a time): a job of
     several models -- or a test-suite -- then finds them in the cache instead of compiling them one after the other at
     construction.  specs: dicts with the arguments of a from_source call as `BK_SOURCE_RECORD=<file>` logs them
-    (user_source, form, contract, dims, head, stage).  Returns (built or found, failed); `errors`: a list that receives
+    (user_source, form, contract, dims, head, stage; neighbour, false where absent).  Returns (built or found, failed); `errors`: a list that receives
     (form, dims, message tail) of every failed build."""
     import os
     from concurrent.futures import ThreadPoolExecutor
@@ -611,7 +621,7 @@ def prewarm_sources(specs, workers=None, errors=None):
     seen, todo = set(), []
     for sp in specs:
         key = (sp["user_source"], sp["form"], bool(sp.get("contract", False)), int(sp["dims"]), int(sp.get("head", 0)),
-               sp.get("stage", "auto"))
+               sp.get("stage", "auto"), bool(sp.get("neighbour", False)))
         if key not in seen:
             seen.add(key)
             todo.append(key)
@@ -781,7 +791,7 @@ def _bind_source_fast_paths(t):
 
 
 def _ctarget_from_source(cls, source: str, dims: int, params=None, form: str = "elementwise", contract: bool = False,
-                         ops=None, head: int = 0, stage: str = "auto"):
+                         ops=None, head: int = 0, stage: str = "auto", neighbour: bool = False):
     """A device model from a few lines of HIP C++, compiled with hipcc when the object is built (cached by content
     in a private per-user directory: $XDG_CACHE_HOME/bayes_kit_amd or ~/.cache/bayes_kit_amd, BK_SOURCE_TARGET_DIR
     overrides; a directory or cached library that another user could have written is refused) into the plugin ABI --
@@ -801,7 +811,16 @@ def _ctarget_from_source(cls, source: str, dims: int, params=None, form: str = "
     with ``c.dims()``, ``c.head(i)``, ``c.sum(f)``, ``c.grad_head(i, g)``, ``c.grad(f)`` (``f(double theta_d, i64 d)``).  A
     chain is served by 4 / 8 / 16 lanes of a wavefront, sums reduced by DPP in a fixed order; with dims - head <= 128
     ``DrGhmcDiag`` runs every delayed-rejection proposal as ONE launch (the path ``bk.Funnel`` has), else the counted
-    step-by-step path.  form="chain": any density; ``source`` defines
+    step-by-step path.  ``neighbour=True`` (form="lanes" only; ValueError elsewhere): rows coupled to their neighbour --
+    AR(1) and state-space models, random-walk priors, stochastic volatility, 1-D GMRF / Markov GP priors -- on the same
+    kernels.  The context then also has ``c.sum_pair(f)``, the canonical-order sum over the spread rows d >= head of
+    ``f(double xp, double x, i64 d)`` with ``xp`` = theta_{d-1} (0.0 for d == head), and ``c.grad_pair(f)``: ``f(xp, x, d)`` returns
+    ``bk_pair{dxp, dx}``, the partials of row d's terms by theta_{d-1} and theta_d, and the library forms
+    g_d = dx(d) + dxp(d+1) in that order (the last row dx(D-1) alone, row head's dxp discarded); called once and last,
+    instead of ``c.grad``.  ``c.sum``, ``c.head``, ``c.grad_head``, ``c.wants_logp`` work as without the flag; separable row
+    terms (observations of x_d) go into ``dx``.  In any other build the two calls fail to compile.  With dims - head > 128
+    a neighbour build has no one-launch leapfrog step (the samplers run the gradient op and the library's kick + drift).
+    form="chain": any density; ``source`` defines
         ``__device__ double bk_chain(const BkTheta& th, const BkGrad& g, i64 D, const double* params)``
     called by one lane per chain (``th[d]``, ``g.set(d, v)``); the chain's coordinates are staged before the call -- in the
     lane's registers for dims <= 128 (the function's loops over d are then unrolled completely), in LDS for dims <= 300; ``stage="lds"``
@@ -815,12 +834,13 @@ def _ctarget_from_source(cls, source: str, dims: int, params=None, form: str = "
     against {gradient op, library kick + drift} on random points and are DROPPED (with a warning; the samplers then run the
     gradient as a separate op) if they disagree: ``chain_hooks_note`` says what happened.
     contract=False compiles with -ffp-contract=off (every product and sum rounded, as NumPy does)."""
-    lib = _compile_source_target(source, form, contract, dims, head, stage)
+    lib = _compile_source_target(source, form, contract, dims, head, stage, bool(neighbour))
     if params is not None and not (isinstance(params, torch.Tensor) and params.dtype == torch.float64):
         raise TypeError("params must be a float64 torch tensor (device memory the compiled function reads) or None")
     t = cls(lib, "bk_src_target", dims, params=params, ops=ops, counted_symbol="bk_src_target_n")
     t.source_library = lib
     t.source_form = form
+    t.source_neighbour = bool(neighbour)
     t._head = int(head)
     _bind_source_fast_paths(t)
     t.chain_hooks_note = _check_chain_hooks(t) if form == "chain" else None

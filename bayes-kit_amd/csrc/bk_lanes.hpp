@@ -20,6 +20,23 @@
 //                               (a trajectory context advances the row as its gradient is delivered; a sum() after
 //                               grad() traps)
 //
+// A density whose rows are coupled to their NEIGHBOUR (AR(1) / state-space models, random-walk priors, 1-D GMRFs) is built
+// with CTarget.from_source(..., form="lanes", neighbour=True) (BK_SOURCE_NEIGHBOUR; the density declares NEIGHBOUR = true)
+// and gets two more calls, which fail to compile (static_assert) in any other build:
+//
+//     c.sum_pair(f)             sum over the spread rows d >= HEAD of f(xp, x, d) -> double, x = theta_d, xp = theta_{d-1}
+//                               (xp = 0.0 for d == HEAD), in the canonical order below (class of row d)
+//     c.grad_pair(f)            f(xp, x, d) -> bk_pair{dxp, dx}: the partials of row d's terms by theta_{d-1} and theta_d.
+//                               The library forms g_d = dx(d) + dxp(d+1) in that order, the last row gets dx(D-1) alone,
+//                               row HEAD's dxp is discarded.  Called ONCE and LAST, instead of c.grad (every partial is
+//                               formed at the pre-drift point before any row of the chain drifts).
+//
+// c.sum, c.head, c.grad_head and c.wants_logp behave as above and may be mixed with c.sum_pair.  Separable row terms (an
+// observation of x_d) go into dx.  Only first-order coupling: the pair term of row d sees theta_{d-1} and theta_d alone.
+// The trajectory kernels fetch row d - 1 with DPP moves inside the chain's lanes (once per leapfrog step, shared by every
+// sum_pair and grad_pair of the step); the gradient op reads it from memory.  With D - HEAD > 128 a neighbour build has no
+// in-place leapfrog step (bk_src_leapfrog_step): the samplers run the gradient op and the library's kick + drift instead.
+//
 // The integrator text is the library's: bayes_kit/drghmc.py:253-289 (leapfrog), :319-346 (proposal map),
 // :391-446 (accept recursion, first ghost) are kernels of THIS header, instantiated once for the built-in funnel
 // (bk_targets.hip) and once per CTarget.from_source(form="lanes") density (the generated translation unit includes
@@ -43,7 +60,23 @@
 #include <math.h>
 #include <stdlib.h>
 
+// what c.grad_pair's function returns for row d: the partials of the row's terms by theta_{d-1} (dxp) and theta_d (dx)
+struct bk_pair {
+  double dxp, dx;
+};
+
 namespace bkl {
+
+// does the density couple neighbouring rows (static constexpr bool NEIGHBOUR = true)?  Densities without the member: no
+template <class DEN, class = void>
+struct NeighbourOf {
+  static constexpr bool value = false;
+};
+template <class DEN>
+struct NeighbourOf<DEN, decltype((void)DEN::NEIGHBOUR)> {
+  static constexpr bool value = DEN::NEIGHBOUR;
+};
+#define BKL_NEIGHBOUR_ONLY "c.sum_pair / c.grad_pair need a neighbour build: CTarget.from_source(..., form=\"lanes\", neighbour=True) (BK_SOURCE_NEIGHBOUR)"
 
 constexpr int WAVES = 4;
 constexpr int CLASSES = 16;
@@ -144,12 +177,47 @@ __device__ __forceinline__ void class_sums(double* cs, const bool* tail_ok, T&& 
   }
 }
 
+// ---- the neighbour halo of a trajectory (neighbour builds): row d - 1 and row d + 1 of a lane's slot u -------------
+// Row d - 1 of class c > 0 is class c - 1, same slot: the lane before in the chain's group, same register slot.  Row d - 1 of
+// class 0 is class 15, one slot earlier: for the group's first lane (the WRAP lane) that is the group's last lane, register slot
+// prev_wrap(u).  Every slot is rotated once (FWD: lane p reads lane p - 1 of its group, the first lane the last one) and the wrap
+// lane takes the rotation of its previous slot; with 8 lanes per chain two groups share a DPP row and the wrap lanes need a
+// rotation of their own (row_ror 9: lanes 7 and 15 to lanes 0 and 8).  Row d + 1 is the mirror image (BWD, next_wrap).
+template <int LPC>
+struct Halo;
+template <>
+struct Halo<4> {
+  static constexpr int FWD = 0x93, FWD_WRAP = 0x93;  // quad_perm [3,0,1,2]
+  static constexpr int BWD = 0x39, BWD_WRAP = 0x39;  // quad_perm [1,2,3,0]
+};
+template <>
+struct Halo<8> {
+  static constexpr int FWD = 0x121, FWD_WRAP = 0x129;  // row_ror 1, row_ror 9
+  static constexpr int BWD = 0x12F, BWD_WRAP = 0x127;  // row_ror 15, row_ror 7
+};
+template <>
+struct Halo<16> {
+  static constexpr int FWD = 0x121, FWD_WRAP = 0x121;  // row_ror 1
+  static constexpr int BWD = 0x12F, BWD_WRAP = 0x12F;  // row_ror 15
+};
+// register slot u = k*SL + i holds class (pos + LPC k), slot i.  The wrap lane's row d - 1 / d + 1 sits in the other end lane's
+// slot prev_wrap(u) / next_wrap(u); -1: none (row HEAD has no row before it, the last slot of class 15 none after it)
+template <int KC, int SL>
+__host__ __device__ constexpr int prev_wrap(int u) {
+  return u / SL > 0 ? u - SL : (u % SL > 0 ? (KC - 1) * SL + u % SL - 1 : -1);
+}
+template <int KC, int SL>
+__host__ __device__ constexpr int next_wrap(int u) {
+  return u / SL < KC - 1 ? u + SL : (u % SL + 1 < SL ? u % SL + 1 : -1);
+}
+
 // ---- the lane context of a trajectory: rows in registers, the gradient delivered INTO the kick -----------------
 //   r  += hk * (metric * grad)            (drghmc.py:277 / :281 / :286)
 //   x  += hd * r     when DRIFT           (drghmc.py:278 / :282)
 //   g_out <- grad    when STORE           (the proposal's end point keeps its gradient, drghmc.py:285)
 // MTR: the 16-lane geometry keeps its rows' metric entries in registers (<= 8 rows), the others re-read them (L1).
-template <int LPC, int SL, bool HM, int HEAD, bool STORE, bool DRIFT>
+// NB: a neighbour build (sum_pair / grad_pair).
+template <int LPC, int SL, bool HM, int HEAD, bool STORE, bool DRIFT, bool NB = false>
 struct TrajCtx {
   using G = Geo<LPC, SL>;
   static constexpr int NU = G::NU, KC = G::KC;
@@ -171,6 +239,8 @@ struct TrajCtx {
   uint32_t bo_out;
   bool on;
   bool rows_done;
+  double xpc[NB ? NU : 1];  // NB: row d - 1 of every slot, formed once per leapfrog step (xp_ready)
+  bool xp_ready;
 
   __device__ __forceinline__ i64 dims() const { return D; }
   __device__ __forceinline__ double head(int i) const { return v[i]; }
@@ -209,6 +279,67 @@ struct TrajCtx {
       }
       // bound the live temporaries (registers -> occupancy)
       if (DRIFT && LPC != 16 && (u & 3) == 3) __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+
+  // ---- neighbour builds --------------------------------------------------------------------------------------------
+  // row d - 1 of slot u at the current (pre-drift) point: the previous lane's slot u, for the wrap lane the last lane's slot
+  // prev_wrap(u) (0.0 for row HEAD).  All 64 lanes are active here (lanes past the set compute on chain 0).
+  __device__ __forceinline__ double halo_fwd(int u) const {
+    using H = Halo<LPC>;
+    const int pu = prev_wrap<KC, SL>(u);
+    const double w = pu < 0 ? 0.0 : dpp_f64_all<H::FWD_WRAP>(x[pu < 0 ? 0 : pu]);
+    const double a = dpp_f64_all<H::FWD>(x[u]);
+    return pos == 0 ? w : a;
+  }
+  __device__ __forceinline__ void halo() {
+    if (xp_ready) return;  // (folds away: a compile-time constant after inlining)
+    xp_ready = true;
+#pragma unroll
+    for (int u = 0; u < NU; ++u) xpc[NB ? u : 0] = halo_fwd(u);
+  }
+  template <class F>
+  __device__ __forceinline__ double sum_pair(F&& f) {
+    static_assert(NB && sizeof(F) > 0, BKL_NEIGHBOUR_ONLY);
+    if (rows_done) __builtin_trap();
+    halo();
+    double cs[KC];
+    class_sums<G, SL>(cs, tail_ok, [&](int u) { return f(xpc[NB ? u : 0], x[u], row(u)); });
+    return reduce_lanes<LPC>(cs);
+  }
+  // All partials at the pre-drift point, delivered into kick + drift: the slots are walked in DESCENDING canonical row order
+  // (slot i from the last one down, within it class k from the last one down: the rows p + LPC k + 16 i of all the chain's lanes
+  // at once).  Row d - 1 of every row of the step is then still undrifted (the previous lane's same slot is read before anything
+  // of it moves, the wrap lane's slot prev_wrap(u) -- class k - 1, or the last class one slot earlier -- comes later), and row
+  // d + 1's dxp is there already (the next lane's same slot, just formed, or the wrap lane's slot next_wrap(u) -- class k + 1, or
+  // the first class one slot later -- came earlier): one pass, and of the dxp only the pending ones stay live.
+  template <class F>
+  __device__ __forceinline__ void grad_pair(F&& f) {
+    static_assert(NB && sizeof(F) > 0, BKL_NEIGHBOUR_ONLY);
+    using H = Halo<LPC>;
+    if (rows_done) __builtin_trap();
+    rows_done = true;
+    double dxp[NU];
+#pragma unroll
+    for (int w = NU - 1; w >= 0; --w) {
+      const int u = (w % KC) * SL + w / KC;  // w = i KC + k
+      const double xp = xp_ready ? xpc[NB ? u : 0] : halo_fwd(u);
+      bk_pair q = {0.0, 0.0};
+      if (ok(u)) q = f(xp, x[u], row(u));
+      dxp[u] = q.dxp;
+      const int nu = next_wrap<KC, SL>(u);
+      const double nw = nu < 0 ? 0.0 : dpp_f64_all<H::BWD_WRAP>(dxp[nu < 0 ? 0 : nu]);
+      const double na = dpp_f64_all<H::BWD>(q.dxp);
+      const double nx = pos == LPC - 1 ? nw : na;
+      if (ok(u)) {
+        const double gi = row(u) + 1 < D ? q.dx + nx : q.dx;  // g_d = dx(d) + dxp(d + 1); the last row dx alone
+        const double t = HM ? metric_of(u) * gi : gi;
+        r[u] = r[u] + hk * t;
+        if (DRIFT) x[u] = x[u] + hd * r[u];
+        if (STORE && on && g_out)
+          *reinterpret_cast<double*>(reinterpret_cast<char*>(g_out + (i64)G::off(u) * ld_out) + bo_out) = gi;
+      }
+      if (DRIFT && LPC != 16 && (w & 3) == 0) __builtin_amdgcn_sched_barrier(0);
     }
   }
 };
@@ -336,9 +467,10 @@ __device__ __forceinline__ void traj_body(const TrajArgs& a, i64 n, const bk_gho
       v[i] = v[i] + h * rv[i];
     }
   }
-  using StepCtx = TrajCtx<LPC, SL, HM, HEAD, false, true>;
-  using KickCtx = TrajCtx<LPC, SL, HM, HEAD, false, false>;
-  using EndCtx = TrajCtx<LPC, SL, HM, HEAD, true, false>;
+  constexpr bool NB = NeighbourOf<DEN>::value;
+  using StepCtx = TrajCtx<LPC, SL, HM, HEAD, false, true, NB>;
+  using KickCtx = TrajCtx<LPC, SL, HM, HEAD, false, false, NB>;
+  using EndCtx = TrajCtx<LPC, SL, HM, HEAD, true, false, NB>;
   if (regrad) {
     // no cached gradient of the source point was handed over: evaluate it here and deliver it into the first half-kick +
     // drift (drghmc.py:276-278).  The same operations on the same values as the branch above -- the gradient is a function
@@ -694,7 +826,10 @@ struct CoopRed {
 // SL > 0: a wavefront's rows of its 64 chains sit in registers (one batch of loads, no second pass: on a small lane set a
 // launch is a chain of memory round trips).  SL = 0: any D, the rows are walked in memory (sums, then gradient).
 // STEP: the gradient is delivered INTO kick + drift, rho and theta rewritten in place (bk_leapfrog_step); else stored.
-template <int SL, bool HM, int HEAD, bool STEP>
+// NB: a neighbour build.  Row d - 1 / d + 1 belongs to another wavefront: read from memory (in cache), and with STEP k_lane_op
+// holds every write until all wavefronts are done reading.  A pair term is evaluated by the row it belongs to and, for its dxp,
+// once more by the row before (same function, same arguments: same bits).  SL = 0 has no in-place step.
+template <int SL, bool HM, int HEAD, bool STEP, bool NB = false>
 struct OpCtx {
   using G = Geo<4, (SL > 0 ? SL : 1)>;
   static constexpr int NU = SL > 0 ? G::NU : 1, KC = G::KC;
@@ -784,6 +919,59 @@ struct OpCtx {
       }
     }
   }
+
+  // ---- neighbour builds --------------------------------------------------------------------------------------------
+  __device__ __forceinline__ double prev_row(i64 d) const { return d == HEAD ? 0.0 : th[(d - 1) * ld]; }
+  template <class F>
+  __device__ __forceinline__ double sum_pair(F&& f) {
+    static_assert(NB && sizeof(F) > 0, BKL_NEIGHBOUR_ONLY);
+    if (rows_done) __builtin_trap();
+    double cs[KC];
+    if constexpr (SL > 0) {
+      class_sums<G, SL>(cs, tail_ok, [&](int u) { return f(prev_row(row(u)), x[u], row(u)); });
+    } else {
+#pragma unroll
+      for (int k = 0; k < KC; ++k) {
+        double acc = 0.0;
+#pragma unroll 4
+        for (i64 d = HEAD + pos + 4 * k; d < D; d += CLASSES) acc = acc + f(prev_row(d), th[d * ld], d);
+        cs[k] = acc;
+      }
+    }
+    return red(cs);
+  }
+  template <class F>
+  __device__ __forceinline__ void grad_pair(F&& f) {
+    static_assert(NB && sizeof(F) > 0, BKL_NEIGHBOUR_ONLY);
+    static_assert(!(STEP && SL == 0), "a neighbour build has no in-place leapfrog step for D - HEAD > 128");
+    if (rows_done) __builtin_trap();
+    rows_done = true;
+    if (!STEP && !g) return;
+    if constexpr (SL > 0) {
+#pragma unroll
+      for (int u = 0; u < NU; ++u)
+        if (ok(u)) {
+          const i64 d = row(u);
+          double gi = f(prev_row(d), x[u], d).dx;
+          if (d + 1 < D) gi = gi + f(x[u], th[(d + 1) * ld], d + 1).dxp;  // g_d = dx(d) + dxp(d + 1)
+          if (STEP) {
+            const double t = HM ? metric[d] * gi : gi;
+            r[u] = r[u] + h * t;
+            x[u] = x[u] + h * r[u];
+          } else if (on) {
+            g[d * ld] = gi;
+          }
+        }
+    } else {
+#pragma unroll 4
+      for (i64 d = HEAD + pos; d < D; d += 4) {
+        const double xd = th[d * ld];
+        double gi = f(prev_row(d), xd, d).dx;
+        if (d + 1 < D) gi = gi + f(xd, th[(d + 1) * ld], d + 1).dxp;
+        if (on) g[d * ld] = gi;
+      }
+    }
+  }
 };
 
 // gradient op (STEP = false: g and / or logp out) or one leapfrog step in place (STEP = true) for min(n, *n_dev) chains
@@ -791,7 +979,8 @@ template <class DEN, int SL, bool HM, bool STEP>
 __global__ __launch_bounds__(BLOCK) void k_lane_op(double* th, double* rho, double* g, double* logp, i64 ld, const double* metric,
                                                    double h, const double* params, i64 n_host, i64 D, const uint32_t* n_dev) {
   constexpr int HEAD = DEN::HEAD;
-  using C = OpCtx<SL, HM, HEAD, STEP>;
+  constexpr bool NB = NeighbourOf<DEN>::value;
+  using C = OpCtx<SL, HM, HEAD, STEP, NB>;
   using G = typename C::G;
   constexpr int H1 = HEAD > 0 ? HEAD : 1, SLq = SL > 0 ? SL : 1;
   __shared__ double part[2][WAVES][BK_WAVE];
@@ -827,8 +1016,8 @@ __global__ __launch_bounds__(BLOCK) void k_lane_op(double* th, double* rho, doub
       logp != nullptr, CoopRed{part, w, lane, 0}, false};
   const double lp = DEN::eval(c, params);
   // (a density without a sum() has no barrier of its own: every wavefront must have read the head coordinates before
-  // wavefront 0 rewrites them)
-  if (STEP && HEAD > 0) __syncthreads();
+  // wavefront 0 rewrites them -- and in a neighbour build the rows of the other wavefronts before any row is rewritten)
+  if (STEP && (HEAD > 0 || NB)) __syncthreads();
   if (!on) return;
   if (STEP) {
     if constexpr (SL > 0) {
@@ -936,4 +1125,5 @@ static int step_launch(double* theta, double* rho, int64_t ld, const double* met
 }
 #undef BKL_OP_SWITCH
 
+#undef BKL_NEIGHBOUR_ONLY
 }  // namespace bkl
