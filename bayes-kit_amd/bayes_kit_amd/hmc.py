@@ -30,8 +30,6 @@ from ._engine import ManyChainSampler
 
 class HMCDiag(ManyChainSampler):
     TUNING = ("graph", "prefetch_rng", "tune_placement", "chain_tile")
-    ENABLE_FUSED_DRAW = True  # experiments / bisection: the one-pass draw kernel for built-in targets
-    ENABLE_FUSED_ZT = True    # ... and its chain-major momentum input
 
     def __init__(
         self,
@@ -82,14 +80,13 @@ class HMCDiag(ManyChainSampler):
             self._install_metric_dense(metric_dense)
             fuse_builtin = False
         self._init_graph(graph, prefetch_rng)
-        # built-in separable targets can run the whole trajectory in registers
-        # (bk_hmc_trajectory_gaussian); results are bit-identical to the step-by-step path
-        self._fused = bool(fuse_builtin) and self._batched and hasattr(model, "bk_hmc_trajectory")
-        # ... and, where the target can also sum the energies along the way (bk_hmc_draw_gaussian),
-        # a draw is: generator, ONE pass over the state (trajectory + kin0 + kin1 + end-point log
-        # density), accept, select.  With Philox streams the momentum is consumed chain-major,
-        # straight from the wavefront-per-chain generator: no transpose, no kinetic-energy pass.
-        self._fused_draw = self._fused and hasattr(model, "bk_hmc_draw") and self.ENABLE_FUSED_DRAW
+        # built-in separable targets (and separable densities compiled from source) run the whole draw in
+        # registers (bk_hmc_draw_gaussian): generator, ONE pass over the state (trajectory + kin0 + kin1 +
+        # end-point log density), accept, select; results are bit-identical to the step-by-step path.  With
+        # Philox streams the momentum is consumed chain-major, straight from the wavefront-per-chain
+        # generator: no transpose, no kinetic-energy pass.
+        self._fused_draw = (bool(fuse_builtin) and self._batched and self._M is None and hasattr(model, "bk_hmc_draw"))
+        self._fused = self._fused_draw  # whole-trajectory kernels in use: the whole draw is the only such path
         # ... a lane-spread density (bk.Funnel, CTarget.from_source(form="lanes")) runs the whole trajectory -- gradient
         # inlined, theta / rho register-resident, the proposal's gradient, log density and kinetic energy out -- as ONE launch
         # (bk_hmc_proposal: the delayed-rejection proposal kernel with hmc.py's first kick); the step-by-step path otherwise
@@ -99,8 +96,7 @@ class HMCDiag(ManyChainSampler):
         # ... and ONE launch per trajectory where it has bk_leapfrog_trajectory (a per-chain density compiled from source:
         # theta in registers, rho in LDS through all L steps), followed by the library's finish launch
         self._traj_hook = (bool(fuse_builtin) and self._step_hook and hasattr(model, "bk_leapfrog_trajectory"))
-        self._fused_zt = (self._fused_draw and self._rng_kind == _lib.RNG_PHILOX and self._dim >= 32
-                          and self.ENABLE_FUSED_ZT)
+        self._fused_zt = self._fused_draw and self._rng_kind == _lib.RNG_PHILOX and self._dim >= 32
         D, C, dev = self._dim, self._C, self._ops.device
         f64 = dict(dtype=torch.float64, device=dev)
         self._rho_bufs = [None if self._fused_zt else torch.empty((D, C), **f64)]
@@ -395,17 +391,6 @@ class HMCDiag(ManyChainSampler):
             m_draw = None if (m is None or self._metric_identity) else m
             self._model.bk_hmc_draw(th, thp, rho, zt, m_draw, eps, L, self._part, kin0, self._kin1, self._lp_p,
                                     accept=(self._lp, logu, self._mask, self._ret, self._accepted))  # [hmc.py:56-63]
-            self._take(th, thp)
-            return
-        if self._fused:
-            if not self._have_cache:
-                self._eval_logp(th, self._lp)
-                self._have_cache = True
-            self._model.bk_hmc_trajectory(th, thp, rho, rho, m, eps, L)        # [hmc.py:40-53]
-            ops.leapfrog_finish(rho, None, None, m, 0.0, False, self._kin1)    # kinetic term [hmc.py:37]
-            self._eval_logp(thp, self._lp_p)
-            ops.mh_accept(_lib.ACCEPT_HMC, self._lp, kin0, self._lp_p, self._kin1, logu,
-                          self._mask, self._ret, self._accepted)
             self._take(th, thp)
             return
 

@@ -107,10 +107,6 @@ class IsoGaussian(_GaussianLanes, _BuiltinTarget):
 
     _kind = "iso_gaussian"
 
-    def bk_hmc_trajectory(self, theta_in, theta_out, rho_in, rho_out, metric, eps, steps):
-        """Whole leapfrog trajectory with the gradient inlined (register-resident)."""
-        self._get_ops().hmc_trajectory_gaussian(theta_in, theta_out, rho_in, rho_out, None, metric, eps, steps)
-
     def bk_hmc_draw(self, theta_in, theta_out, rho_in, zt, metric, eps, steps, part, kin0, kin1, lp_out, accept=None):
         """Trajectory + energies (+ accept test) of one HMC draw in one pass (bk_hmc_draw_gaussian)."""
         self._get_ops().hmc_draw_gaussian(theta_in, theta_out, rho_in, zt, None, metric, eps, steps, part, kin0, kin1,
@@ -138,11 +134,6 @@ class DiagGaussian(_GaussianLanes, _BuiltinTarget):
     def bk_eval(self, theta_dc, grad_out, logp_out, n_dev=None):
         self._lam(theta_dc.device)
         super().bk_eval(theta_dc, grad_out, logp_out, n_dev)
-
-    def bk_hmc_trajectory(self, theta_in, theta_out, rho_in, rho_out, metric, eps, steps):
-        """Whole leapfrog trajectory with the gradient inlined (register-resident)."""
-        self._get_ops().hmc_trajectory_gaussian(theta_in, theta_out, rho_in, rho_out, self._lam(theta_in.device),
-                                                metric, eps, steps)
 
     def bk_hmc_draw(self, theta_in, theta_out, rho_in, zt, metric, eps, steps, part, kin0, kin1, lp_out, accept=None):
         """Trajectory + energies (+ accept test) of one HMC draw in one pass (bk_hmc_draw_gaussian)."""
@@ -648,8 +639,8 @@ def prewarm_sources(specs, workers=None, errors=None):
 
 
 def _bind_source_fast_paths(t):
-    """Attach the whole-proposal / whole-draw hooks the samplers look for (bk_dr_proposal, bk_hmc_draw,
-    bk_hmc_trajectory) when the generated library exports them: the same hooks the built-in targets have."""
+    """Attach the whole-proposal / whole-draw hooks the samplers look for (bk_dr_proposal, bk_hmc_draw) when the
+    generated library exports them: the same hooks the built-in targets have."""
     import ctypes
     import types
 
@@ -671,7 +662,6 @@ def _bind_source_fast_paths(t):
     def stream(x):
         return torch.cuda.current_stream(x.device).cuda_stream if x.is_cuda else None
 
-    f_traj = export("bk_src_hmc_trajectory", [P, P, P, P, I, P, P, F, I, I, I, P])
     f_draw = export("bk_src_hmc_draw", [P, P, I, P, P, I, P, P, F, I, P, P, P, P, P, P, P, P, P, I, I, P])
     f_prop = export("bk_src_dr_proposal_job", [P, P, P, I, P, P, P, P, P, P, I, P, F, I, I, I, P, P, P, P, P, P, P, P, P, P, P])
 
@@ -738,16 +728,6 @@ def _bind_source_fast_paths(t):
             return True
 
         t.bk_hmc_proposal = types.MethodType(bk_hmc_proposal, t)
-    if f_traj is not None:
-        def bk_hmc_trajectory(self, theta_in, theta_out, rho_in, rho_out, metric, eps, steps):
-            """Whole leapfrog trajectory with the compiled term inlined (register-resident; bk_elementwise.hpp)."""
-            D, C = theta_in.shape
-            ld = _lib._ld(theta_in)
-            assert _lib._ld(theta_out) == ld and _lib._ld(rho_in) == ld and _lib._ld(rho_out) == ld
-            check(f_traj(ptr(theta_in), ptr(theta_out), ptr(rho_in), ptr(rho_out), ld, self._pp, ptr(metric), eps, steps,
-                         C, D, stream(theta_in)), "bk_src_hmc_trajectory")
-
-        t.bk_hmc_trajectory = types.MethodType(bk_hmc_trajectory, t)
     if f_draw is not None:
         def bk_hmc_draw(self, theta_in, theta_out, rho_in, zt, metric, eps, steps, part, kin0, kin1, lp_out, accept=None):
             """Trajectory + energies (+ accept test) of one HMC draw in one pass, the compiled term inlined."""
@@ -803,7 +783,7 @@ def _ctarget_from_source(cls, source: str, dims: int, params=None, form: str = "
     form="elementwise": the log density is a sum over coordinates; ``source`` defines
         ``__device__ void bk_term(double th, i64 d, const double* params, double& term, double& grad)``
     and the library supplies the kernels: a streaming 16-byte-per-lane gradient kernel, per-chain sums in the library's
-    own order, and the register-resident whole-trajectory / whole-draw HMC kernels the built-in Gaussians have
+    own order, and the register-resident whole-draw HMC kernel the built-in Gaussians have
     (``HMCDiag`` then runs a draw as generator + ONE pass over the state, bit-identical to the step-by-step path).
     form="lanes": a density of head coordinates and sums over the other ("spread") rows -- hierarchical models;
     ``head`` = number of leading coordinates every lane holds; ``source`` defines
@@ -1023,8 +1003,8 @@ class TorchModel:
         # the hooks the samplers look for, straight to the compiled target
         self.bk_eval, self.bk_counted = target.bk_eval, target.bk_counted
         self.compiled_form = form
-        for name in ("bk_hmc_draw", "bk_hmc_trajectory", "bk_leapfrog_step", "bk_leapfrog_trajectory", "bk_hmc_proposal",
-                     "bk_dr_proposal", "bk_dr_proposal_supported", "bk_mala_step"):
+        for name in ("bk_hmc_draw", "bk_leapfrog_step", "bk_leapfrog_trajectory", "bk_hmc_proposal", "bk_dr_proposal",
+                     "bk_dr_proposal_supported", "bk_mala_step"):
             if hasattr(target, name):
                 setattr(self, name, getattr(target, name))
         self.__dict__.pop("bk_gradient", None)

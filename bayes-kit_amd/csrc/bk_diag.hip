@@ -534,8 +534,6 @@ int bk_rank_normalize(const double* rank, double S, double* out, int64_t n, void
 // one chain does not fit (the one-lane-per-chain kernels then serve).
 static int ess_tile_launch(const double* x, i64 ld, i64 N, int estimator, double* ess_out, double* iat_out,
                            double* acor_out, i64 ldo, i64 C, hipStream_t s) {
-  static const bool lane_only = []() { const char* e = getenv("BK_ESS_LANE_PER_CHAIN"); return e && e[0] == '1'; }();
-  if (lane_only) return 0;  // experiments: the one-lane-per-chain kernels
   const bool rt = N >= ET_RT_MIN_DRAWS;
   const int pitch = (int)((rt ? N + ET_RT_TAIL : N) | 1);
   const i64 cap = (i64)(160 * 1024 - 512) / 8;

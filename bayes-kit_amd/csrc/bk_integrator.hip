@@ -8,7 +8,6 @@
 // traffic.  The library is compiled with -ffp-contract=off: no FMA, every product and sum
 // is rounded separately, exactly like the NumPy expressions of the reference.
 #include "bk_common.hpp"
-#include <stdlib.h>
 
 namespace {
 
@@ -602,9 +601,7 @@ int bk_leapfrog_kick_drift(const double* theta_in, double* theta_out, const doub
     if (vec) {
       // Streams much larger than the 256 MiB Infinity Cache use non-temporal loads/stores
       // (measured +8 % on MI355X: 6.49 vs 6.0 TB/s); cache-resident tiles use plain
-      // accesses (7.1 TB/s out of the Infinity Cache).  BK_KD_VARIANT overrides (tuning).
-      static const int forced = []() { const char* e = getenv("BK_KD_VARIANT"); return e ? atoi(e) : -1; }();
-      int v = forced >= 0 ? forced : (bk_streams_past_llc(5 * C * D) ? 4 : 5);
+      // accesses (7.1 TB/s out of the Infinity Cache).
 #define BK_KD_LAUNCH(ROWS, NT)                                                                          \
   do {                                                                                                  \
     dim3 grid((unsigned)bk_cdiv(C / 2, KD_BLOCK), (unsigned)bk_cdiv(D, ROWS));                          \
@@ -612,15 +609,10 @@ int bk_leapfrog_kick_drift(const double* theta_in, double* theta_out, const doub
                                                               grad, ldg_d, metric, eps, use_pre, pre,   \
                                                               use_kick, kick, C / 2, D);                \
   } while (0)
-      switch (v) {
-        case 1: BK_KD_LAUNCH(2, false); break;
-        case 2: BK_KD_LAUNCH(8, false); break;
-        case 3: BK_KD_LAUNCH(4, true); break;
-        case 4: BK_KD_LAUNCH(2, true); break;
-        case 5: BK_KD_LAUNCH(1, false); break;
-        case 6: BK_KD_LAUNCH(1, true); break;
-        default: BK_KD_LAUNCH(4, false); break;
-      }
+      if (bk_streams_past_llc(5 * C * D))
+        BK_KD_LAUNCH(2, true);
+      else
+        BK_KD_LAUNCH(1, false);
 #undef BK_KD_LAUNCH
       BK_RETURN_LAUNCH_STATUS();
     }

@@ -22,10 +22,10 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // A workgroup holds PAIRS chain pairs x all dimensions: 64 * PAIRS threads, thread (j, r) = (t % PAIRS, t / PAIRS) the rows
 // r, r + 64, ... of pair j.  PAIRS = 8 is k_mala_step's shape (16 chains, 128-byte row segments, the whole register file of a
-// CU) and the one that runs.  PAIRS = 4 (8 chains, 64-byte segments, one wavefront per SIMD; BK_MALA_STEP_PAIRS=4) leaves room
-// for a wavefront of the normals' generator beside it on every SIMD: measured at 65,536 x 1,024 the two kernels then do overlap,
-// and each takes about twice as long (step 514 -> 847 us, generator 454 -> 863 us; alone the narrow step takes 681 us) -- 0.97 ms
-// per draw either way (profiles/r5_mala.md).  Same summation order for both shapes.
+// CU) and the only one launched.  PAIRS = 4 (8 chains, 64-byte segments, one wavefront per SIMD) leaves room for a wavefront of
+// the normals' generator beside it on every SIMD: measured at 65,536 x 1,024 the two kernels then do overlap, and each takes
+// about twice as long (step 514 -> 847 us, generator 454 -> 863 us; alone the narrow step takes 681 us) -- 0.97 ms per draw
+// either way (profiles/r5_mala.md).  Same summation order for both shapes.
 constexpr int MS_ROWS = 64;  // rows per slot
 constexpr unsigned RSRC_FLAGS = 0x00020000u;    // raw buffer, 32-bit data format (gfx90a / gfx94x / gfx950)
 
@@ -217,22 +217,16 @@ static int mala_step_sep_launch(const double* theta, double* theta_out, double* 
   if (!bk_aligned16(theta) || !bk_aligned16(theta_out) || !bk_aligned16(theta_prop)) return BK_E_ALIGN;
   if (zt_next && (ldz < D || ldz % 2 != 0 || !bk_aligned16(zt_next))) return BK_E_ALIGN;
   hipStream_t s = bk_stream(stream);
-  // BK_MALA_STEP_PAIRS=4: the narrow workgroups of the note on PAIRS above (experiments)
-  static const int pairs = []() { const char* e = getenv("BK_MALA_STEP_PAIRS"); return (e && atoi(e) == 4) ? 4 : 8; }();
+  constexpr int P = 8;  // chain pairs per workgroup (the note on PAIRS above)
   const bool nt = bk_streams_past_llc(4 * C * D);
-#define BKM_LAUNCH2(E, NT, P)                                                                                            \
+#define BKM_LAUNCH2(E, NT)                                                                                               \
   k_mala_step_sep<TERM, E, NT, P><<<dim3((unsigned)bk_cdiv(C, 2 * P)), dim3(64 * P), 0, s>>>(                            \
       theta, theta_out, theta_prop, ld, params, lp, lp_prop, log_u, zt_next, ldz, eps, sqrt2eps, accept_mask, ret, accept_count, C, \
       D)
-#define BKM_LAUNCH(E)                  \
-  do {                                 \
-    if (pairs == 8) {                  \
-      if (nt) BKM_LAUNCH2(E, true, 8); \
-      else BKM_LAUNCH2(E, false, 8);   \
-    } else {                           \
-      if (nt) BKM_LAUNCH2(E, true, 4); \
-      else BKM_LAUNCH2(E, false, 4);   \
-    }                                  \
+#define BKM_LAUNCH(E)             \
+  do {                            \
+    if (nt) BKM_LAUNCH2(E, true); \
+    else BKM_LAUNCH2(E, false);   \
   } while (0)
   if (D <= 128) BKM_LAUNCH(2);
   else if (D <= 256) BKM_LAUNCH(4);

@@ -491,8 +491,6 @@ __device__ __forceinline__ void zig_parallel_wave(uint64_t* st, i64 ldr, double*
 // several wavefronts the smallest product wins.  Small launches are latency bound: fewest passes
 // first, then the fewest lanes (8.1 vs 9.6 us at 1000 x 70 with 32 instead of 64 lanes per chain).
 static int zp_lanes_per_chain(i64 C, i64 D) {
-  static const int forced = []() { const char* e = getenv("BK_ZP_LANES"); return e ? atoi(e) : 0; }();
-  if (forced == 16 || forced == 32 || forced == 64) return forced;
   const double words = 1.0085 * (double)D + 6.0;  // a chain's D normals take ~0.85 % extra words
   const bool fills = C >= 8192;                    // LPC = 64 then gives >= 8 wavefronts per SIMD
   int best = 64;
@@ -789,8 +787,7 @@ static void refresh_apply_kin_launch(const double* work, i64 dp, const double* l
                                      double* out, i64 ld, const double* metric, double* kin_out, i64 C, i64 D,
                                      const DrBegin& b, hipStream_t s) {
   const size_t lds = (size_t)(64 * (dp + 1) + 256) * sizeof(double);
-  static const bool rows_off = getenv("BK_REFRESH_ROWS_OFF") != nullptr;  // (A/B with tools/cfg4_profile_run.py)
-  if (dp <= 128 && lds <= 65536 && !rows_off)
+  if (dp <= 128 && lds <= 65536)
     k_refresh_apply_kin_rows<BEGIN><<<dim3((unsigned)bk_cdiv(C, 64)), dim3(256), lds, s>>>(work, dp, loc_in, loc_mul, scale,
                                                                                           out, ld, metric, kin_out, C, D, b);
   else

@@ -11,7 +11,6 @@
 #include "bk_elementwise.hpp"
 #include "bk_mala_step.hpp"
 #include "bk_lanes.hpp"
-#include <stdlib.h>
 
 namespace {
 
@@ -208,22 +207,7 @@ int gauss(const double* theta, double* grad, double* logp, i64 ld, const double*
   }
   if (D == 0) return BK_OK;
   if (C % 2 == 0 && ld % 2 == 0 && bk_aligned16(theta) && bk_aligned16(grad)) {
-    static const int forced = []() { const char* e = getenv("BK_GG_VARIANT"); return e ? atoi(e) : -1; }();
-    if (forced >= 0) {  // tuning only
-#define BK_GG(ROWS, NT)                                                                      \
-  do {                                                                                       \
-    dim3 grid((unsigned)bk_cdiv(C / 2, TG_BLOCK), (unsigned)bk_cdiv(D, ROWS));                \
-    k_gauss_grad_v2<ROWS, NT><<<grid, dim3(TG_BLOCK), 0, s>>>(theta, grad, ld, lam, C / 2, D); \
-  } while (0)
-      switch (forced) {
-        case 1: BK_GG(1, true); break;
-        case 2: BK_GG(2, true); break;
-        case 3: BK_GG(8, true); break;
-        case 4: BK_GG(4, false); break;
-        default: BK_GG(4, true); break;
-      }
-#undef BK_GG
-    } else if (bk_streams_past_llc(2 * C * D) && D <= 65535) {
+    if (bk_streams_past_llc(2 * C * D) && D <= 65535) {
       // one row per thread, non-temporal: 6.5 TB/s vs 6.1 with four rows (MI355X, 1 GiB streams)
       dim3 grid((unsigned)bk_cdiv(C / 2, TG_BLOCK), (unsigned)D);
       k_gauss_grad_v2<1, true><<<grid, dim3(TG_BLOCK), 0, s>>>(theta, grad, ld, lam, C / 2, D);

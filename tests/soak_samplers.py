@@ -19,10 +19,6 @@ from tests import provider_parity as pp
 from tests.host_models import Ar1
 
 
-if os.environ.get("SOAK_NO_FUSED_DRAW"):
-    bk.HMCDiag.ENABLE_FUSED_DRAW = False
-if os.environ.get("SOAK_NO_FUSED_ZT"):
-    bk.HMCDiag.ENABLE_FUSED_ZT = False
 MALA_KW = dict(two_pass=False) if os.environ.get("SOAK_NO_TWO_PASS") else {}
 
 

@@ -176,7 +176,7 @@ def test_torch_model_compile_flag_on_the_build_box(cache_tmp_path, monkeypatch):
     lam_here = lam.to("cuda") if torch.cuda.is_available() else lam
     m = bk.TorchModel(lambda Th: -0.5 * (Th * Th * lam_here).sum(dim=1), D, compile=True)
     assert m.compiled is not None and m.compile_note is None and "bk_term" in m.traced_source
-    assert m.bk_counted and hasattr(m, "bk_eval") and hasattr(m, "bk_hmc_draw") and hasattr(m, "bk_hmc_trajectory")
+    assert m.bk_counted and hasattr(m, "bk_eval") and hasattr(m, "bk_hmc_draw")
     assert os.path.exists(m.compiled.source_library)
     with pytest.warns(UserWarning, match="logsumexp"):
         u = bk.TorchModel(lambda Th: torch.logsumexp(Th * lam, dim=1), D, compile=True)

@@ -1,7 +1,7 @@
 """bk_dr_proposal_funnel alone (HIP events): one whole delayed-rejection proposal on Neal's funnel for n chains of
 a 32,768-chain parent set, at the (lanes, steps) of config 4's seven trajectories.  `dev=1` passes the lane
 count in device memory (launch sized for the parent set, 16 lanes per chain), `dev=0` on the host.
-    python tools/funnel_traj_bench.py            # BK_FUNNEL_GEOMETRY=wide|narrow to force a geometry"""
+    python tools/funnel_traj_bench.py"""
 import json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "bayes-kit_amd")]
@@ -47,5 +47,5 @@ for tag, n, h, steps in [("P0", 32768, 0.2, 10), ("P1", 4091, 0.05, 40), ("G0(P1
     res.append({"traj": tag, "lanes": n, "steps": steps, "us": round(us, 2), "us_one_step": round(us1, 2),
                 "us_per_extra_step": round((us - us1) / (steps - 1), 3),
                 "gflops_13D": round(n * steps * 13.0 * D / us / 1e3, 1)})
-print(json.dumps({"D": D, "pad": PAD, "lib": os.environ.get("BK_LIB"), "geometry_env": os.environ.get("BK_FUNNEL_GEOMETRY"), "trajectories": res,
+print(json.dumps({"D": D, "pad": PAD, "lib": os.environ.get("BK_LIB"), "trajectories": res,
                   "sum_us": round(sum(r["us"] for r in res), 1)}))

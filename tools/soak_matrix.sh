@@ -8,8 +8,6 @@ for v in "$@"; do
   case $v in
     all_on) run all_on X=1;;
     no_two_pass) run no_two_pass SOAK_NO_TWO_PASS=1;;
-    no_fused_draw) run no_fused_draw SOAK_NO_FUSED_DRAW=1;;
-    no_fused_zt) run no_fused_zt SOAK_NO_FUSED_ZT=1;;
     no_graph) run no_graph SOAK_NO_GRAPH=1;;
     no_prefetch) run no_prefetch SOAK_NO_PREFETCH=1;;
     no_graph_no_prefetch) run no_graph_no_prefetch SOAK_NO_GRAPH=1 SOAK_NO_PREFETCH=1;;
