@@ -104,13 +104,21 @@ SIGNATURES = {
     "bk_sort_by_key": [P, P, P, P, I, P, I, P],
     "bk_count_below": [P, I, P, I, P, P],
     "bk_scatter_ranks": [P, I, F, P, P],
+    "bk_ess_multi_work_bytes": [I, I, I],
+    "bk_ess_split_moments": [P, I, I, I, c_int, F, P, P, P, P, I, P],
+    "bk_ess_between_sq": [P, I, P, P, P, I, P],
+    "bk_ess_lag_sums_max_half": [],
+    "bk_ess_lag_sums": [P, I, I, I, c_int, F, P, I, I, P, P, I, P],
+    "bk_ess_acov_sums": [P, I, I, I, P, I, I, P, P, I, P],
+    "bk_ess_indicator": [P, I, I, I, F, P, I, P],
+    "bk_select_ranks": [P, P, I, P, I, P, P],
     "bk_host_normals": [c_int, P, P, I],
     "bk_host_uniforms": [c_int, P, P, I],
     "bk_host_log1p": [F],
     "bk_host_exp": [F],
 }
 _RESTYPE = {"bk_gemm_chains_work_elems": c_int64, "bk_host_log1p": c_double, "bk_host_exp": c_double, "bk_refresh_work_elems": c_int64, "bk_sort_by_key_work_bytes": c_int64,
-             "bk_autocorr_fft_work_bytes": c_int64}
+             "bk_autocorr_fft_work_bytes": c_int64, "bk_ess_multi_work_bytes": c_int64, "bk_ess_lag_sums_max_half": c_int64}
 
 
 class BkHipError(RuntimeError):
@@ -818,6 +826,58 @@ class Ops:
     def ess(self, x, estimator, ess_out, iat_out=None):
         N, C = x.shape
         self._call("bk_ess", ptr(x), _ld(x), N, estimator, ptr(ess_out), ptr(iat_out), C, self._s())
+
+    # -- multi-chain ESS (split chains: rows [0, N // 2) and [N - N // 2, N) of every column) ------------------------
+    def _ess_work(self, n, C, nlags, device):
+        nb = int(self.lib.bk_ess_multi_work_bytes(n, C, nlags))
+        if nb < 0:
+            raise BkHipError("bk_ess_multi_work_bytes failed")
+        return torch.empty(nb // 8, dtype=torch.float64, device=device)
+
+    def ess_lag_sums_max_half(self):
+        return int(self.lib.bk_ess_lag_sums_max_half())
+
+    def ess_split_moments(self, x, q, chain_mean, chain_g0):
+        """-> [3] device tensor (sum of the split chains' means, sum of their gamma_0, count of non-finite draws);
+        q None = the draws themselves, else the indicator x <= q."""
+        N, C = x.shape
+        out = torch.empty(3, dtype=torch.float64, device=x.device)
+        work = self._ess_work(N // 2, C, 1, x.device)
+        self._call("bk_ess_split_moments", ptr(x), _ld(x), N, C, 0 if q is None else 1, 0.0 if q is None else float(q),
+                   ptr(chain_mean), ptr(chain_g0), ptr(out), ptr(work), work.numel() * 8, self._s())
+        return out
+
+    def ess_between_sq(self, chain_mean, centre):
+        out = torch.empty(1, dtype=torch.float64, device=chain_mean.device)
+        work = self._ess_work(1, chain_mean.numel(), 1, chain_mean.device)
+        self._call("bk_ess_between_sq", ptr(chain_mean), chain_mean.numel(), ptr(centre), ptr(out), ptr(work),
+                   work.numel() * 8, self._s())
+        return out
+
+    def ess_lag_sums(self, x, q, chain_mean, lag0, nlags):
+        """-> [nlags] device tensor: sum over the split chains of gamma_{m,t}, t = lag0 .. lag0 + nlags - 1."""
+        N, C = x.shape
+        out = torch.empty(nlags, dtype=torch.float64, device=x.device)
+        work = self._ess_work(N // 2, C, nlags, x.device)
+        self._call("bk_ess_lag_sums", ptr(x), _ld(x), N, C, 0 if q is None else 1, 0.0 if q is None else float(q),
+                   ptr(chain_mean), lag0, nlags, ptr(out), ptr(work), work.numel() * 8, self._s())
+        return out
+
+    def ess_acov_sums(self, acor, chain_g0, lag0, nlags):
+        n, C = acor.shape
+        out = torch.empty(nlags, dtype=torch.float64, device=acor.device)
+        work = self._ess_work(n, C, nlags, acor.device)
+        self._call("bk_ess_acov_sums", ptr(acor), _ld(acor), n, C, ptr(chain_g0), lag0, nlags, ptr(out), ptr(work),
+                   work.numel() * 8, self._s())
+        return out
+
+    def ess_indicator(self, x, q, out):
+        n, C = x.shape
+        self._call("bk_ess_indicator", ptr(x), _ld(x), n, C, float(q), ptr(out), _ld(out), self._s())
+
+    def select_ranks(self, rank, values, targets, out):
+        self._call("bk_select_ranks", ptr(rank), ptr(values), rank.numel(), ptr(targets), targets.numel(), ptr(out),
+                   self._s())
 
 
 _default_ops = None

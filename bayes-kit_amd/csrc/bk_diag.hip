@@ -3,12 +3,15 @@
 // iat.py:7-43,95-135, autocorr.py:6-33).
 #include "bk_common.hpp"
 #include "bk_welford.hpp"
+#include "bk_ess_tile.hpp"
 #include <stdlib.h>
 
 namespace {
 
 using bkw::EL_ROWS;
 using bkw::welford_elem;
+using bke::ess_fold;
+using bke::wave_sum;
 constexpr int PC_BLOCK = 64;
 
 __global__ __launch_bounds__(256) void k_welford(double* mean, double* m2, const double* th, i64 ld, i64 ld_th,
@@ -201,12 +204,6 @@ __global__ __launch_bounds__(PC_BLOCK) void k_autocorr(const double* x, i64 ld, 
 // Work per chain: O(N * ceil(lags/64)); all lags (bk_autocorr): O(N^2 / 64) per wavefront.
 constexpr int ET_BLOCK = 256, ET_WAVES = ET_BLOCK / BK_WAVE;
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int m = 1; m < BK_WAVE; m <<= 1) v = v + __shfl_xor(v, m);
-  return v;
-}
-
 // RT (series of ET_RT_MIN_DRAWS draws and more): a block of 64 lags is summed from REGISTER TILES instead of one LDS read
 // per multiply-add.  Lane l owns 9 consecutive draws t = tc + 9 l + b of every chunk of 576 draws and keeps 64
 // accumulators, one per lag of the block; a chunk needs the lane's 9 values x[t..t+8] and the window
@@ -215,18 +212,6 @@ __device__ __forceinline__ double wave_sum(double v) {
 // need no masks.  A butterfly of 63 exchanges then leaves the total of lag n0 + l in lane l (the layout the Geyer scan
 // below works on).  Per-lag order of summation: a lane's draws ascending, then a fixed tree over the lanes.
 constexpr int ET_RT_MIN_DRAWS = 288, ET_RT_TAIL = 72;
-
-template <int HALF>
-__device__ __forceinline__ void ess_fold(double (&v)[64], int lane) {
-  // lanes whose bit HALF is set keep the upper half of the first 2*HALF entries, the others the lower half
-#pragma unroll
-  for (int i = 0; i < HALF; ++i) {
-    const bool up = (lane & HALF) != 0;
-    const double send = up ? v[i] : v[i + HALF];
-    const double mine = up ? v[i + HALF] : v[i];
-    v[i] = mine + __shfl_xor(send, HALF);
-  }
-}
 
 template <int G, bool RT>
 __global__ __launch_bounds__(ET_BLOCK) void k_ess_tile(const double* x, i64 ld, i64 N, int pitch, int estimator,

@@ -784,6 +784,41 @@ int bk_end_pos_pairs(const double* acor, int64_t ld, int64_t N, int64_t* out, in
 int bk_ess(const double* x, int64_t ld, int64_t N, int estimator, double* ess_out,
            double* iat_out, int64_t C, void* stream);
 
+/* ---- multi-chain ESS (Vehtari, Gelman, Simpson, Carpenter and Buerkner 2021, "Rank-normalization, folding, and
+ * localization: an improved R-hat for assessing convergence of MCMC", Bayesian Analysis 16(2), sec. 3.2, eqs. 10-11;
+ * Stan's compute_effective_sample_size) -- the device parts of bulk / tail / mean ESS over all chains.
+ * Split set: column c of the [N, C] series x[t*ld + c] gives the chains rows [0, n) and rows [N - n, N), n = N / 2;
+ * chain m = h * C + c (h = half), M = 2 C.  indicator != 0 reads every draw as (x <= q) ? 1 : 0.  Sums over chains are
+ * per-workgroup partials reduced in a fixed order: repeated calls are bit-identical.  work: caller scratch of
+ * bk_ess_multi_work_bytes(n, C, nlags) bytes (nlags = the largest lag count of a call; 1 for the moments). */
+int64_t bk_ess_multi_work_bytes(int64_t n, int64_t C, int64_t nlags);
+/* Per split chain chain_mean[m] and gamma_{m,0} = (1/n) sum_i (x_{m,i} - mean_m)^2 (chain_g0[m]), [2C] each;
+ * out[0] = sum_m mean_m, out[1] = sum_m gamma_{m,0}, out[2] = number of non-finite draws (of x itself). */
+int bk_ess_split_moments(const double* x, int64_t ld, int64_t N, int64_t C, int indicator, double q, double* chain_mean,
+                         double* chain_g0, double* out, void* work, int64_t work_bytes, void* stream);
+/* out[0] = sum_m (chain_mean[m] - centre[0])^2 over M chains (the second pass of the between-chain variance around a
+ * centre gathered over all ranks). */
+int bk_ess_between_sq(const double* chain_mean, int64_t M, const double* centre, double* out, void* work,
+                      int64_t work_bytes, void* stream);
+/* Cross-chain lag sums out[t - lag0] = sum_m gamma_{m,t}, gamma_{m,t} = (1/n) sum_{i < n - t} (x_{m,i} - mean_m)
+ * (x_{m,i+t} - mean_m), for t in [lag0, lag0 + nlags) (lag0 + nlags <= n); chain_mean from bk_ess_split_moments.  The
+ * chains are staged in LDS once (one wavefront per chain, 64 lags per pass, register tiles from 288 draws on) for every
+ * requested lag; a request whose per-workgroup partials would pass 256 MiB runs as several launches.  Halves longer than
+ * bk_ess_lag_sums_max_half() return BK_E_ARG: bk_autocorr_fft on the half views, then bk_ess_acov_sums. */
+int64_t bk_ess_lag_sums_max_half(void);
+int bk_ess_lag_sums(const double* x, int64_t ld, int64_t N, int64_t C, int indicator, double q, const double* chain_mean,
+                    int64_t lag0, int64_t nlags, double* out, void* work, int64_t work_bytes, void* stream);
+/* out[t - lag0] = sum_c chain_g0[c] * acor[t*ldo + c] over C chains of an autocorrelation array (bk_autocorr_fft of one
+ * half, a batch of chains); chains with chain_g0 = 0 (constant) contribute 0. */
+int bk_ess_acov_sums(const double* acor, int64_t ldo, int64_t n, int64_t C, const double* chain_g0, int64_t lag0,
+                     int64_t nlags, double* out, void* work, int64_t work_bytes, void* stream);
+/* out[t*ldo + c] = (x[t*ld + c] <= q) ? 1 : 0, t < n: the indicator chains for the FFT route of tail ESS. */
+int bk_ess_indicator(const double* x, int64_t ld, int64_t n, int64_t C, double q, double* out, int64_t ldo, void* stream);
+/* Order statistics by global rank (the quantile of tail ESS across ranks): out[j] = values[i] for the element whose 1-based
+ * rank[i] equals targets[j], j < k <= 8; other entries of out are left alone (zero them, then sum over ranks). */
+int bk_select_ranks(const double* rank, const double* values, int64_t n, const double* targets, int64_t k, double* out,
+                    void* stream);
+
 /* ---- host-side self-test hooks (tests only; they run the SAME source as the kernels on
  * the host so the RNG can be checked against numpy without a GPU).  Host pointers. */
 int bk_host_normals(int rng_kind, uint64_t* state_words /*[BK_RNG_WORDS]*/, double* out,
