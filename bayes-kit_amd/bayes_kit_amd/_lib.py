@@ -32,10 +32,13 @@ SIGNATURES = {
     "bk_rng_init_philox": [P, I, c_uint64, c_uint64, I, P],
     "bk_refresh_work_elems": [I, I],
     "bk_momentum_refresh": [c_int, P, I, P, F, F, P, I, P, P, P, I, I, P, I, P],
+    "bk_momentum_refresh_precond": [c_int, P, I, P, I, P, P, I, I, P, I, P],
     "bk_log_uniform": [c_int, P, I, P, P, I, P],
     "bk_uniform": [c_int, P, I, P, P, I, P],
     "bk_leapfrog_kick_drift": [P, P, P, P, I, P, I, I, P, F, c_int, F, c_int, F, I, I, P],
     "bk_leapfrog_finish": [P, P, I, P, I, I, P, F, c_int, P, I, I, P],
+    "bk_precond_pack": [P, P, I, P],
+    "bk_leapfrog_finish_precond": [P, P, I, P, I, I, P, F, c_int, P, I, I, P],
     "bk_leapfrog_kick_drift_n": [P, P, P, P, I, P, I, I, P, F, c_int, F, c_int, F, I, I, P, P],
     "bk_leapfrog_first_step_gather": [P, P, P, I, P, P, P, I, P, F, F, I, I, P, P],
     "bk_leapfrog_finish_level": [P, P, I, P, I, I, P, F, c_int, P, I, I, P, P, P, P, P, P, P, P],
@@ -76,6 +79,7 @@ SIGNATURES = {
     "bk_hmc_trajectory_funnel": [P, P, P, P, P, P, P, I, P, F, I, I, I, P],
     "bk_hmc_trajectory_gaussian": [P, P, P, P, I, P, P, F, I, I, I, P],
     "bk_hmc_draw_gaussian": [P, P, I, P, P, I, P, P, F, I, P, P, P, P, P, P, P, P, P, I, I, P],
+    "bk_hmc_draw_gaussian_precond": [P, P, I, P, P, I, P, P, F, I, P, P, P, P, P, P, P, P, P, I, I, P],
     "bk_dr_proposal_funnel": [P, P, P, I, P, P, P, P, P, P, I, P, F, I, I, I, P, P, P, P, P, P, P, P, P, P],
     "bk_dense_metric_apply": [P, I, P, P, I, I, I, P],
     "bk_gemm_chains": [P, I, I, I, P, I, P, I, I, P, I, P],
@@ -91,6 +95,7 @@ SIGNATURES = {
     "bk_record_series_dev": [P, I, P, I, P, P, I, P, I, I, P],
     "bk_welford_update_dev": [P, P, I, P, I, P, I, I, I, P],
     "bk_rhat_partials": [P, P, I, I, P, P, I, I, P],
+    "bk_accept_stat": [P, P, P, P, I, P, P, P],
     "bk_chain_mean_var": [P, I, P, I, P, P, I, P],
     "bk_end_pos_pairs": [P, I, I, P, I, P],
     "bk_ess": [P, I, I, c_int, P, P, I, P],
@@ -314,6 +319,13 @@ class Ops:
                    ptr(out), _ld(out), ptr(metric), ptr(kin_out), ptr(active), C, D, ptr(work),
                    0 if work is None else work.numel(), self._s())
 
+    def momentum_refresh_precond(self, kind, state, out, precond, kin_out, work=None):
+        """out = 0.0 + sqrt(v)*z and its kinetic energy 1/2 out.(out/v); precond: the packed [3, D] {v, sqrt(v), 1/v}."""
+        D, C = out.shape
+        assert precond.is_contiguous() and tuple(precond.shape) == (3, D)
+        self._call("bk_momentum_refresh_precond", kind, ptr(state), state.stride(0), ptr(out), _ld(out), ptr(precond),
+                   ptr(kin_out), C, D, ptr(work), 0 if work is None else work.numel(), self._s())
+
     def log_uniform(self, kind, state, out, active=None):
         self._call("bk_log_uniform", kind, ptr(state), state.stride(0), ptr(out), ptr(active),
                    out.shape[0], self._s())
@@ -364,6 +376,31 @@ class Ops:
         self._call("bk_leapfrog_finish_level", ptr(rho_in), ptr(rho_out), _ld(rho_in), ptr(grad), gs[0], gs[1],
                    ptr(metric), half, int(negate), ptr(kin_out), C, D, ptr(n_dev), ptr(logp), ptr(H), ptr(h),
                    ptr(live), ptr(lanes_out), ptr(lanes_total), self._s())
+
+    def precond_pack(self, v, precond):
+        """precond [3, D] = {v, sqrt(v), 1/v} from the D variances v."""
+        D = v.shape[0]
+        assert v.is_contiguous() and precond.is_contiguous() and tuple(precond.shape) == (3, D)
+        self._call("bk_precond_pack", ptr(v), ptr(precond), D, self._s())
+
+    def leapfrog_finish_precond(self, rho_in, rho_out, grad, precond, half, negate, kin_out):
+        """leapfrog_finish kicking with precond[0] = v and summing the kinetic energy with precond[2] = 1/v."""
+        D, C = rho_in.shape
+        if rho_out is not None:
+            assert _ld(rho_out) == _ld(rho_in)
+        assert precond.is_contiguous() and tuple(precond.shape) == (3, D)
+        gs = (0, 0) if grad is None else grad.stride()
+        self._call("bk_leapfrog_finish_precond", ptr(rho_in), ptr(rho_out), _ld(rho_in), ptr(grad), gs[0], gs[1],
+                   ptr(precond), half, int(negate), ptr(kin_out), C, D, self._s())
+
+    def accept_stat(self, lp_cur, a_cur, lp_prop, a_prop, out, work=None):
+        """out[0] = sum_c min(1, bk_exp(min(0, d_c))), out[1] = number of NaN d_c, d_c = (lp_prop - a_prop) - (lp_cur -
+        a_cur); work: 2 * ceil(C / 256) doubles of scratch (allocated here when not given)."""
+        C = lp_cur.shape[0]
+        if work is None:
+            work = torch.empty(max(2, 2 * ((C + 255) // 256)), dtype=torch.float64, device=lp_cur.device)
+        assert work.numel() >= 2 * ((C + 255) // 256)
+        self._call("bk_accept_stat", ptr(lp_cur), ptr(a_cur), ptr(lp_prop), ptr(a_prop), C, ptr(out), ptr(work), self._s())
 
     def mh_accept(self, mode, lp_cur, a_cur, lp_prop, a_prop, log_u, mask, ret, count):
         self._call("bk_mh_accept", mode, ptr(lp_cur), ptr(a_cur), ptr(lp_prop), ptr(a_prop), ptr(log_u),
@@ -602,7 +639,7 @@ class Ops:
                    ptr(lam), ptr(metric), eps, steps, C, D, self._s())
 
     def hmc_draw_gaussian(self, theta_in, theta_out, rho_in, zt, lam, metric, eps, steps, part, kin0, kin1, lp_out,
-                          accept=None):
+                          accept=None, precond=None):
         """Trajectory + both kinetic energies + end-point log density of one HMC draw; momentum from
         rho_in ([D, C]) or from chain-major normals zt ([C, >=D]), exactly one of them.
         accept: optional (lp_cur, log_u, mask, ret, count) -- the draw's accept test in the same launches
@@ -615,7 +652,11 @@ class Ops:
             assert zt.shape[0] == C and zt.stride(1) == 1 and zt.shape[1] >= D
             ldz = zt.stride(0)
         lp_cur, log_u, mask, ret, count = accept if accept is not None else (None,) * 5
-        self._call("bk_hmc_draw_gaussian", ptr(theta_in), ptr(theta_out), ld, ptr(rho_in), ptr(zt), ldz, ptr(lam),
+        name = "bk_hmc_draw_gaussian"
+        if precond is not None:  # a proper diagonal preconditioner, packed [3, D] {v, sqrt(v), 1/v}, in place of the metric
+            assert metric is None and precond.is_contiguous() and tuple(precond.shape) == (3, D)
+            name, metric = "bk_hmc_draw_gaussian_precond", precond
+        self._call(name, ptr(theta_in), ptr(theta_out), ld, ptr(rho_in), ptr(zt), ldz, ptr(lam),
                    ptr(metric), eps, steps, ptr(part), ptr(kin0), ptr(kin1), ptr(lp_out), ptr(lp_cur), ptr(log_u),
                    ptr(mask), ptr(ret), ptr(count), C, D, self._s())
 

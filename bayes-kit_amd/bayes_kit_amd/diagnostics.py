@@ -39,14 +39,15 @@ def _gather_sum(t: torch.Tensor, group=None) -> torch.Tensor:
     return gather_sum(t, group)
 
 
-def rhat_from_moments(mean_dc, m2_dc, n: int, ops=None, group=None) -> np.ndarray:
-    """Per-dimension R-hat (bayes_kit/rhat.py:163-171) from per-chain Welford moments
-    ``mean, M2`` ([D, C_local] each, n draws per chain), over ALL ranks' chains.
+def _cross_chain_moments(mean_dc, m2_dc, n: int, ops, group=None, ieee_division=False):
+    """-> (mean over all ranks' chains of the per-chain variances, variance (ddof = 1) of the per-chain means), device
+    tensors [D], from per-chain Welford moments ``mean, M2`` ([D, C_local] each, n draws per chain).
 
     Two passes, like ``np.var(means, ddof=1)``: first sum(mean) and sum(var) -> grand mean;
     then sum((mean - grand mean)^2).  Each pass is one kernel + one tiny all_gather.
+    ieee_division: divide by the chain count as a TENSOR (PyTorch divides a device tensor by a host scalar by multiplying
+    with its reciprocal, which is one ulp off the quotient for some values): the same doubles on every device.
     """
-    ops = _ops(ops)
     D, C = mean_dc.shape
     dev = mean_dc.device
     if n < 2:
@@ -58,14 +59,30 @@ def rhat_from_moments(mean_dc, m2_dc, n: int, ops=None, group=None) -> np.ndarra
     M = float(tot[3 * D].item())
     if M < 2:
         raise ValueError(f"rhat requires len(chains) >= 2, but len(chains) = {int(M)}")
-    centre = (tot[0:D] / M).contiguous()
-    mean_var = tot[D:2 * D] / M
+    Md = tot[3 * D:3 * D + 1] if ieee_division else M
+    centre = (tot[0:D] / Md).contiguous()
+    mean_var = tot[D:2 * D] / Md
     part2 = torch.zeros(3 * D + 1, dtype=torch.float64, device=dev)
     ops.rhat_partials(mean_dc, m2_dc, n, centre, part2)
     tot2 = _gather_sum(part2, group)
-    var_means = tot2[2 * D:3 * D] / (M - 1.0)
+    var_means = tot2[2 * D:3 * D] / (Md - 1.0)
+    return mean_var, var_means
+
+
+def rhat_from_moments(mean_dc, m2_dc, n: int, ops=None, group=None) -> np.ndarray:
+    """Per-dimension R-hat (bayes_kit/rhat.py:163-171) from per-chain Welford moments
+    ``mean, M2`` ([D, C_local] each, n draws per chain), over ALL ranks' chains."""
+    mean_var, var_means = _cross_chain_moments(mean_dc, m2_dc, n, _ops(ops), group)
     nf = float(n)
     return torch.sqrt((nf - 1.0) / nf + var_means / mean_var).cpu().numpy()
+
+
+def pooled_variance_from_moments(mean_dc, m2_dc, n: int, ops=None, group=None) -> torch.Tensor:
+    """Per-dimension variance of the draws of all chains of all ranks pooled, from the same moments and the same two
+    passes as R-hat: (n-1)/n * mean_c(var_c) + var_c(mean_c), both ddof = 1.  A device tensor [D]."""
+    mean_var, var_means = _cross_chain_moments(mean_dc, m2_dc, n, _ops(ops), group, ieee_division=True)
+    nf = float(n)
+    return (nf - 1.0) / nf * mean_var + var_means
 
 
 def _as_dc(theta, D: int, C: int, layout=None):
@@ -131,6 +148,17 @@ class RunningMoments:
 
     def rhat(self, group=None) -> np.ndarray:
         return rhat_from_moments(self.mean, self.m2, self.n, self._ops, group)
+
+    def pooled_variance(self, group=None) -> np.ndarray:
+        """Per-dimension variance of all draws seen so far, pooled over the chains of all ranks:
+        (n-1)/n * mean_c(var_c) + var_c(mean_c), both ddof = 1 (needs n >= 2 draws and >= 2 chains, as rhat)."""
+        return pooled_variance_from_moments(self.mean, self.m2, self.n, self._ops, group).cpu().numpy()
+
+    def reset(self) -> None:
+        """Forget every draw: the moments start again from nothing."""
+        self.mean.zero_()
+        self.m2.zero_()
+        self.n = 0
 
     # checkpoint / resume (SURVEY 8f.4): the Welford state is (n, mean, M2); restored, the stream of
     # updates continues bit for bit

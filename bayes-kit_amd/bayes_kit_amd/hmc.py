@@ -44,6 +44,7 @@ class HMCDiag(ManyChainSampler):
         chain_id0: int = 0,
         path: str = "auto",
         metric_dense=None,
+        precond_diag=None,
         tuning: Optional[dict] = None,
         ops=None,
         **knobs,
@@ -52,13 +53,28 @@ class HMCDiag(ManyChainSampler):
         ops) and ``metric_dense`` (extension: a dense velocity covariance, fp64 MFMA GEMMs).  Tuning knobs (none changes a
         result): ``graph`` (replay a draw as one hipGraph; default: small launch-bound shapes), ``prefetch_rng`` (the next
         draw's randomness on a side stream; default on), ``tune_placement`` (time which allocation plays which role),
-        ``chain_tile`` (chains per Infinity-Cache tile)."""
+        ``chain_tile`` (chains per Infinity-Cache tile).
+
+        ``precond_diag`` (extension; exclusive with metric_diag and metric_dense): a length-D vector v of velocity variances,
+        ideally the posterior variances -- the proper diagonal preconditioner, ``oracle.samplers.HMCDense`` with M = diag(v)
+        at the cost of the elementwise kernels: rho = 0.0 + sqrt(v)*z, kick rho += eps*(v*grad), kinetic energy
+        1/2 rho.(rho/v).  Every path supports it and gives the same draws bit for bit: the built-in Gaussians and
+        stay on the whole-draw kernel (its preconditioned instantiation), "step" and "opaque" use the preconditioned refresh
+        and finish launches around the unchanged kick/drift kernels.  Two kinds of model fall back to one launch per leapfrog
+        step while a preconditioner is set: a lane-spread density (bk_hmc_proposal sums the kinetic energy inside its
+        launch), and an elementwise from_source / traced density (the whole-draw kernel compiled with it has no
+        preconditioned export; it is HBM-bound there instead of register-resident).  ``set_precond_diag`` replaces it between draws,
+        ``warmup`` estimates it."""
         fuse_builtin, fuse_steps = self._resolve_path(path)
         tn = self._resolve_tuning(tuning, knobs)
         chain_tile, graph = tn.get("chain_tile"), tn.get("graph")
         prefetch_rng, tune_placement = tn.get("prefetch_rng"), tn.get("tune_placement")
         self._stepsize = stepsize
         self._steps = steps
+        self._pd = None        # packed preconditioner [3, D] = {v, sqrt(v), 1/v} on the device (precond_diag)
+        self._stat = None      # warmup(): where a draw leaves its acceptance statistic (bk_accept_stat)
+        if precond_diag is not None and (metric_diag is not None or metric_dense is not None):
+            raise ValueError("give precond_diag or metric_diag / metric_dense, not both")
         self._setup(model, metric_diag, init, seed, chains, chain_id0, ops)
         self._chain_tile = self._pick_tile(chain_tile)
         # Dense metric (extension; the reference only has metric_diag, and its literal
@@ -79,6 +95,8 @@ class HMCDiag(ManyChainSampler):
                 raise ValueError("metric_dense needs a batched device model")
             self._install_metric_dense(metric_dense)
             fuse_builtin = False
+        if precond_diag is not None:
+            self._install_precond(precond_diag)
         self._init_graph(graph, prefetch_rng)
         # built-in separable targets (and separable densities compiled from source) run the whole draw in
         # registers (bk_hmc_draw_gaussian): generator, ONE pass over the state (trajectory + kin0 + kin1 +
@@ -86,6 +104,11 @@ class HMCDiag(ManyChainSampler):
         # Philox streams the momentum is consumed chain-major, straight from the wavefront-per-chain
         # generator: no transpose, no kinetic-energy pass.
         self._fused_draw = (bool(fuse_builtin) and self._batched and self._M is None and hasattr(model, "bk_hmc_draw"))
+        # ... with a preconditioner only where the model has the preconditioned form of that kernel (bk_hmc_draw_precond:
+        # the built-in Gaussians); a density compiled from source (CTarget.from_source, TorchModel(compile=True)) then runs
+        # step by step -- one launch per leapfrog step with its density inlined -- with the same draws bit for bit
+        if self._pd is not None and not hasattr(model, "bk_hmc_draw_precond"):
+            self._fused_draw = False
         self._fused = self._fused_draw  # whole-trajectory kernels in use: the whole draw is the only such path
         # ... a lane-spread density (bk.Funnel, CTarget.from_source(form="lanes")) runs the whole trajectory -- gradient
         # inlined, theta / rho register-resident, the proposal's gradient, log density and kinetic energy out -- as ONE launch
@@ -197,6 +220,60 @@ class HMCDiag(ManyChainSampler):
                 torch.cuda.current_stream().wait_event(self._pf_event)
             self._pf_ready, self._pf_event = False, None
 
+    # -- the proper diagonal preconditioner -----------------------------------------------------------
+    def _install_precond(self, v):
+        """Validate v and form {v, sqrt(v), 1/v} on the device, in place once the buffer exists (a captured hipGraph
+        keeps pointing at it).  The kick kernels see the first row as their metric."""
+        if self._M is not None or (self._pd is None and self._metric_dev is not None):
+            raise ValueError("precond_diag cannot be combined with metric_diag / metric_dense")
+        vt = torch.as_tensor(v, dtype=torch.float64).reshape(-1)
+        if vt.shape[0] != self._dim:
+            raise ValueError(f"precond_diag has {vt.shape[0]} entries, model has {self._dim} dims")
+        vt = vt.to(self._ops.device).contiguous()
+        if not bool((torch.isfinite(vt) & (vt > 0.0)).all()):
+            raise ValueError("precond_diag must hold finite, positive variances")
+        if self._pd is None:
+            self._pd = torch.empty((3, self._dim), dtype=torch.float64, device=self._ops.device)
+            self._metric_dev, self._metric_identity = self._pd[0], False
+            self._drop_graphs()  # the captured launches had no preconditioner: capture again
+        self._ops.precond_pack(vt, self._pd)  # (the library's own sqrt and 1/x: the same doubles on every device)
+
+    def set_precond_diag(self, v):
+        """Set or replace the diagonal preconditioner between draws (see ``precond_diag``).  Changes no stream position:
+        the chain-major generator keeps raw normals, which only their consumer scales; a momentum generated ahead in the
+        state layout (prefetch_rng) carries the old scale, so it is dropped and regenerated from the stream position it
+        started at."""
+        self._install_precond(v)
+        if self._fused_draw and not hasattr(self._model, "bk_hmc_draw_precond"):
+            self._leave_whole_draw()
+        if getattr(self, "_prefetch", False) and self._pf_ready and not self._fused_zt:
+            if self._pf_event is not None:
+                torch.cuda.current_stream().wait_event(self._pf_event)
+            self._rng_state.copy_(self._rng_logical)
+            self._pf_ready, self._pf_event = False, None
+
+    def _leave_whole_draw(self):
+        """From the whole-draw kernel to the step-by-step path between two draws (a preconditioner was set on a model whose
+        whole-draw hook has no preconditioned form): the stream goes back to where the next draw's randomness began, the
+        momentum gets its state-layout buffers, and the cached gradient is evaluated again (the whole-draw path keeps the
+        log density only; the same kernel gives the same value)."""
+        if self._prefetch and self._pf_ready:
+            if self._pf_event is not None:
+                torch.cuda.current_stream().wait_event(self._pf_event)
+            self._rng_state.copy_(self._snap[self._pf_slot] if self._snap is not None else self._rng_logical)
+            self._pf_ready, self._pf_event = False, None
+        self._fused_draw = self._fused = self._fused_zt = False
+        self._rho_bufs = [r if r is not None else torch.empty_like(self._theta_p) for r in self._rho_bufs]
+        if self._prefetch and self._snap is not None:
+            self._snap, self._rng_logical = None, self._rng_state.clone()
+        self._have_cache = False
+        self._drop_graphs()
+
+    @property
+    def precond_diag(self):
+        """The preconditioner's variances as a host array (None when not set)."""
+        return None if self._pd is None else self._pd[0].cpu().numpy().copy()
+
     def _tune_placement(self):
         """Roles (theta', grad', rho of each slot, grad): see ManyChainSampler._tune_roles."""
         ops, m, eps = self._ops, self._metric_dev, float(self._stepsize)
@@ -244,6 +321,8 @@ class HMCDiag(ManyChainSampler):
         return self._mask.bool() if self._batched else bool(self._mask[0].item())
 
     def _set_metric(self, m):
+        if self._pd is not None:
+            raise ValueError("metric_diag cannot be combined with precond_diag")
         super()._set_metric(m)
         self._pf_kin_stale = True  # a prefetched kinetic energy was computed with the old metric
 
@@ -262,10 +341,29 @@ class HMCDiag(ManyChainSampler):
         return self._rng_state
 
     def load_state_dict(self, sd):
+        if getattr(self, "_prefetch", False) and self._pf_ready:
+            torch.cuda.synchronize()  # (the generator queued ahead has finished before its bookkeeping goes)
+            self._pf_ready, self._pf_event = False, None
         if self._rebind:
             # the state array is the last draw handed out (see _draw): restore into a fresh one
             self._theta_dc = torch.empty_like(self._theta_dc)
         super().load_state_dict(sd)
+
+    def _state_extra(self):
+        return {"stepsize": float(self._stepsize), "precond_diag": None if self._pd is None else self._pd[0].cpu().clone()}
+
+    def _load_extra(self, extra):
+        # (checkpoints written before the step size and the preconditioner were carried hold neither: nothing changes)
+        if "stepsize" in extra:
+            self._stepsize = extra["stepsize"]
+        pv = extra.get("precond_diag")
+        if pv is not None:
+            # (randomness generated ahead was dropped by load_state_dict: nothing here moves the restored stream)
+            self._install_precond(pv)
+            if self._fused_draw and not hasattr(self._model, "bk_hmc_draw_precond"):
+                self._leave_whole_draw()
+        elif self._pd is not None and "precond_diag" in extra:
+            raise ValueError("checkpoint was written without precond_diag, this sampler has one")
 
     def _after_load(self):
         # drop any randomness generated ahead: it is regenerated from the restored stream
@@ -286,6 +384,9 @@ class HMCDiag(ManyChainSampler):
             # position while this slot is the one generated ahead -- in snap[slot])
             ops.normals_chain_major(self._rng_kind, self._rng_state, self._zt_bufs[slot], self._dim,
                                     None if self._snap is None else self._snap[slot])
+        elif self._pd is not None:
+            ops.momentum_refresh_precond(self._rng_kind, self._rng_state, self._rho_bufs[slot], self._pd,
+                                         self._kin0_bufs[slot], self._rng_work)
         elif self._M is None:
             ops.momentum_refresh(self._rng_kind, self._rng_state, None, 0.0, 1.0, self._rho_bufs[slot],
                                  self._metric_dev, None if self._fused_draw else self._kin0_bufs[slot], None,
@@ -362,6 +463,86 @@ class HMCDiag(ManyChainSampler):
     def _graph_key(self):
         return (float(self._stepsize), int(self._steps))
 
+    # -- warmup -------------------------------------------------------------------------------------
+    def warmup(self, draws, target_accept=0.8, adapt_metric=True, group=None):
+        """Run `draws` draws that tune the step size and (adapt_metric) the diagonal preconditioner from ALL chains of all
+        ranks, then keep the tuned values: afterwards the sampler samples with them.  -> report dict: ``stepsize``,
+        ``precond_diag`` (host copy, None if none is set), per-draw ``eps`` and ``alpha`` histories, ``window_ends``,
+        ``nan_chains`` (total count of chains whose energy difference was NaN).
+
+        Step size: dual averaging on log(eps) towards a mean acceptance statistic of `target_accept`
+        (adapt.DualAveraging), fed once per draw with mean_c min(1, exp(min(0, h1 - h0))) over every chain
+        (bk_accept_stat; a NaN difference counts 0).  Metric: Welford moments of the state after every draw inside a window
+        of adapt.warmup_windows; at a window's end v = N/(N+5) * pooled variance + 1e-3 * 5/(N+5), N = draws in the window
+        x chains, becomes the preconditioner (set_precond_diag), the moments are reset and the step size restarts from
+        its averaged iterate.  `steps` is not adapted.
+
+        Cost: the statistic kernel, ONE host read of three doubles (summed over ranks in rank order, dist.gather_sum) and,
+        inside windows, a Welford update per draw; two more [D, C] arrays for the window moments, freed at the end.  The
+        draws are launched eagerly (the step size changes every draw); captured graphs are dropped once at the end.  On
+        launch-bound shapes (a draw of tens of microseconds) the host read dominates a warmup draw: at 128 x 4,096 chains a
+        warmup draw takes 0.10 ms against 0.056 for a replayed plain draw, at 1,024 x 65,536 1.6-1.7 ms against 1.2
+        (profiles/warmup_adapt.md).  A model without the preconditioned whole-draw hook (an elementwise from_source or traced
+        density) leaves the whole-draw kernel for one launch per leapfrog step when its first window ends.
+        All ranks reach identical eps and v, and a given (seed, chains, world size) reproduces them bit for bit on every path.
+        Across world sizes the sums are grouped differently and agree to rounding only -- and dual averaging is not a
+        contraction (after a restart it swings the step size across the stability limit and back), so that rounding grows: two
+        world sizes end at different, equally valid adaptations (observed: eps 0.647 against 0.675, v within 3 % of each
+        other and of the truth)."""
+        from .adapt import DualAveraging, warmup_windows
+        from .diagnostics import RunningMoments, _gather_sum, pooled_variance_from_moments
+
+        draws = int(draws)
+        if draws < 1:
+            raise ValueError(f"warmup: draws must be >= 1, got {draws}")
+        if not 0.0 < float(target_accept) < 1.0:
+            raise ValueError(f"warmup: target_accept must be inside (0, 1), got {target_accept}")
+        if adapt_metric and (self._M is not None or (self._pd is None and self._metric_dev is not None)):
+            raise ValueError("warmup: adapt_metric=True estimates precond_diag, which cannot be combined with "
+                             "metric_diag / metric_dense (pass adapt_metric=False to tune the step size alone)")
+        if not self._batched:
+            raise ValueError("warmup needs a batched device model (the statistics are taken across chains)")
+        ops, dev, C, D = self._ops, self._ops.device, self._C, self._dim
+        init, term, ends = warmup_windows(draws)
+        if not adapt_metric:
+            ends = []
+        da = DualAveraging(float(self._stepsize), float(target_accept))
+        mom = RunningMoments(D, C, ops) if ends else None
+        self._stat = torch.zeros(3, dtype=torch.float64, device=dev)  # {sum of the statistic, NaN chains, chains}
+        self._stat[2] = float(C)
+        self._stat_work = torch.empty(max(2, 2 * ((C + 255) // 256)), dtype=torch.float64, device=dev)
+        eps_hist, alpha_hist, nan_chains = [], [], 0
+        try:
+            for it in range(draws):
+                eps_hist.append(float(self._stepsize))
+                self._draw()
+                self._join_side_stream()
+                self._draws += 1
+                tot = _gather_sum(self._stat, group).cpu()  # the warmup draw's one host read
+                chains_total = float(tot[2])
+                alpha = float(tot[0]) / chains_total
+                alpha_hist.append(alpha)
+                nan_chains += int(tot[1])
+                if mom is not None and init <= it < draws - term:
+                    mom.update(self._theta_dc, layout="dc")
+                eps = da.step(alpha)
+                if it + 1 in ends:
+                    n_eff = float(mom.n) * chains_total
+                    var = pooled_variance_from_moments(mom.mean, mom.m2, mom.n, ops, group)
+                    self.set_precond_diag(n_eff / (n_eff + 5.0) * var + 1e-3 * 5.0 / (n_eff + 5.0))
+                    mom.reset()
+                    eps = da.final()
+                    da.restart(eps)
+                if it + 1 == draws:
+                    eps = da.final()
+                self._stepsize = eps
+        finally:
+            self._stat, self._stat_work = None, None
+            del mom
+            self._drop_graphs()
+        return {"stepsize": float(self._stepsize), "precond_diag": self.precond_diag, "eps": eps_hist, "alpha": alpha_hist,
+                "window_ends": list(ends), "nan_chains": nan_chains}
+
     # -- one draw for every chain ------------------------------------------------------------------
     def sample(self):
         self._run_draw(self._draw)
@@ -389,19 +570,26 @@ class HMCDiag(ManyChainSampler):
             zt = self._zt_bufs[self._zt_slot] if self._fused_zt else None
             # (fp64-VALU bound: a metric of ones is not multiplied in -- x * 1.0 is x, bit for bit)
             m_draw = None if (m is None or self._metric_identity) else m
-            self._model.bk_hmc_draw(th, thp, rho, zt, m_draw, eps, L, self._part, kin0, self._kin1, self._lp_p,
-                                    accept=(self._lp, logu, self._mask, self._ret, self._accepted))  # [hmc.py:56-63]
+            accept = (self._lp, logu, self._mask, self._ret, self._accepted)
+            in_launch = accept if self._stat is None else None
+            if self._pd is not None:
+                self._model.bk_hmc_draw_precond(th, thp, rho, zt, self._pd, eps, L, self._part, kin0, self._kin1, self._lp_p,
+                                                accept=in_launch)
+            else:
+                self._model.bk_hmc_draw(th, thp, rho, zt, m_draw, eps, L, self._part, kin0, self._kin1, self._lp_p,
+                                        accept=in_launch)  # [hmc.py:56-63]
+            if in_launch is None:  # warmup: the statistic first, then the same accept arithmetic as its own launch
+                self._accept(kin0, logu)
             self._take(th, thp)
             return
 
-        if self._lanes_traj and L >= 1:
+        if self._lanes_traj and L >= 1 and self._pd is None:
             if not self._have_cache:
                 self._materialize(self._eval_grad(th, self._grad, self._lp), self._grad)
                 self._have_cache = True
             # [hmc.py:40-53, :59] in one launch; the proposal's gradient is kept for the chains that accept
             if self._model.bk_hmc_proposal(th, rho, self._grad, thp, self._grad_p, self._lp_p, self._kin1, m, eps, L):
-                ops.mh_accept(_lib.ACCEPT_HMC, self._lp, kin0, self._lp_p, self._kin1, logu,
-                              self._mask, self._ret, self._accepted)                     # [hmc.py:60-63]
+                self._accept(kin0, logu)                                                 # [hmc.py:60-63]
                 self._take(th, thp, self._grad, self._grad_p)
                 return
 
@@ -458,21 +646,29 @@ class HMCDiag(ManyChainSampler):
                 else:
                     g_last = gl
         # forward half-step + kinetic energy of the proposal [hmc.py:52, :37]
-        if self._M is None:
+        if self._pd is not None:
+            ops.leapfrog_finish_precond(rho, None, g_last, self._pd, half, False, self._kin1)
+        elif self._M is None:
             ops.leapfrog_finish(rho, None, g_last, m, half, False, self._kin1)
         else:
             ops.leapfrog_finish(rho, rho, self._mg(g_last), None, half, False, None)
             self._dense_kinetic(rho, self._kin1, self._mv)
         if mirror:
             self._eval_logp(thp, self._lp_p)                # joint_logp(theta_prop, rho_prop) [hmc.py:59]
-        # accept [hmc.py:60-63]
-        ops.mh_accept(_lib.ACCEPT_HMC, self._lp, kin0, self._lp_p, self._kin1, logu,
-                      self._mask, self._ret, self._accepted)
+        self._accept(kin0, logu)  # [hmc.py:60-63]
         if mirror:
             self._select(self._mask, th, thp)
         else:
             gp = self._materialize(g_last, self._grad_p) if L > 0 else None
             self._take(th, thp, self._grad if gp is not None else None, gp)
+
+    def _accept(self, kin0, logu):
+        """The accept test [hmc.py:60-63]; during warmup() preceded by the acceptance statistic of the same energies
+        (bk_accept_stat, before the test overwrites the current log density)."""
+        if self._stat is not None:
+            self._ops.accept_stat(self._lp, kin0, self._lp_p, self._kin1, self._stat, self._stat_work)
+        self._ops.mh_accept(_lib.ACCEPT_HMC, self._lp, kin0, self._lp_p, self._kin1, logu,
+                            self._mask, self._ret, self._accepted)
 
     def _take(self, th, thp, g=None, gp=None):
         """The accepted chains take their proposal [hmc.py:61] (and its cached gradient)."""

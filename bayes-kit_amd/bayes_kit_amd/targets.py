@@ -112,6 +112,11 @@ class IsoGaussian(_GaussianLanes, _BuiltinTarget):
         self._get_ops().hmc_draw_gaussian(theta_in, theta_out, rho_in, zt, None, metric, eps, steps, part, kin0, kin1,
                                           lp_out, accept)
 
+    def bk_hmc_draw_precond(self, theta_in, theta_out, rho_in, zt, precond, eps, steps, part, kin0, kin1, lp_out, accept=None):
+        """bk_hmc_draw with a proper diagonal preconditioner, the packed [3, D] {v, sqrt(v), 1/v} (bk_hmc_draw_gaussian_precond)."""
+        self._get_ops().hmc_draw_gaussian(theta_in, theta_out, rho_in, zt, None, None, eps, steps, part, kin0, kin1,
+                                          lp_out, accept, precond=precond)
+
 
 class DiagGaussian(_GaussianLanes, _BuiltinTarget):
     """logp = -1/2 sum_i lam_i theta_i^2 (BASELINE.json config 3)."""
@@ -139,6 +144,11 @@ class DiagGaussian(_GaussianLanes, _BuiltinTarget):
         """Trajectory + energies (+ accept test) of one HMC draw in one pass (bk_hmc_draw_gaussian)."""
         self._get_ops().hmc_draw_gaussian(theta_in, theta_out, rho_in, zt, self._lam(theta_in.device), metric, eps,
                                           steps, part, kin0, kin1, lp_out, accept)
+
+    def bk_hmc_draw_precond(self, theta_in, theta_out, rho_in, zt, precond, eps, steps, part, kin0, kin1, lp_out, accept=None):
+        """bk_hmc_draw with a proper diagonal preconditioner, the packed [3, D] {v, sqrt(v), 1/v} (bk_hmc_draw_gaussian_precond)."""
+        self._get_ops().hmc_draw_gaussian(theta_in, theta_out, rho_in, zt, self._lam(theta_in.device), None, eps,
+                                          steps, part, kin0, kin1, lp_out, accept, precond=precond)
 
 
 class Funnel(_BuiltinTarget):

@@ -94,6 +94,8 @@ class EngineTarget(Protocol):
 #                                                           (drghmc.py:280-283, hmc.py:48-50): the step-by-step paths of
 #                                                           DrGhmcDiag and HMCDiag issue one launch per step instead of two
 #   bk_hmc_draw                                             whole HMC draw of a separable density in registers (hmc.py:40-63)
+#   bk_hmc_draw_precond                                     ... with a proper diagonal preconditioner (HMCDiag(precond_diag=v)):
+#                                                           `precond`, the packed [3, D] {v, sqrt(v), 1/v}, in place of the metric
 #   bk_hmc_proposal(theta, rho, grad, theta_out, grad_out, logp_out, kin_out, metric, eps, steps) -> bool
 #                                                           whole HMC trajectory of a lane-spread density as ONE launch
 #   bk_dr_proposal(...) -> bool, bk_dr_proposal_supported() whole delayed-rejection proposal as ONE launch

@@ -454,6 +454,61 @@ __global__ __launch_bounds__(256) void k_record_series(const double* theta, i64 
   series[((i64)k * cap + row) * C + c] = v;
 }
 
+// ---- the acceptance statistic a step-size adaptation averages (bk_accept_stat) -------------------------------------
+// A fixed-shape tree, the same bits on every run: lane = chain, a wavefront's 64 values by the xor butterfly (wave_sum),
+// the four wavefronts of a workgroup as ((w0 + w1) + w2) + w3 -> work[b] (statistic) and work[nb + b] (NaN count); then
+// ONE workgroup: thread t adds partials t, t + 256, ... in that order and the 256 sums go through k_rhat_partials' LDS
+// tree.  No floating-point atomics.
+__global__ __launch_bounds__(256) void k_accept_stat_partials(const double* lp_cur, const double* a_cur,
+                                                              const double* lp_prop, const double* a_prop, i64 C,
+                                                              double* work, i64 nb) {
+  __shared__ double ps[4], pn[4];
+  const i64 c = (i64)blockIdx.x * 256 + threadIdx.x;
+  double a = 0.0, nn = 0.0;
+  if (c < C) {
+    const double a0 = a_cur ? a_cur[c] : 0.0, a1 = a_prop ? a_prop[c] : 0.0;
+    const double h0 = lp_cur[c] - a0, h1 = lp_prop[c] - a1;  // hmc.py:36-38, as k_mh_accept
+    const double d = h1 - h0;
+    if (d != d) nn = 1.0;
+    else a = fmin(1.0, bk_exp(fmin(0.0, d)));
+  }
+  a = wave_sum(a);
+  nn = wave_sum(nn);
+  const int w = bk_wave_id();
+  if ((threadIdx.x & (BK_WAVE - 1)) == 0) {
+    ps[w] = a;
+    pn[w] = nn;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    work[blockIdx.x] = ((ps[0] + ps[1]) + ps[2]) + ps[3];
+    work[nb + blockIdx.x] = ((pn[0] + pn[1]) + pn[2]) + pn[3];
+  }
+}
+
+__global__ __launch_bounds__(256) void k_accept_stat_combine(const double* work, i64 nb, double* out) {
+  __shared__ double red[2][256];
+  double s0 = 0.0, s1 = 0.0;
+  for (i64 b = threadIdx.x; b < nb; b += 256) {
+    s0 = s0 + work[b];
+    s1 = s1 + work[nb + b];
+  }
+  red[0][threadIdx.x] = s0;
+  red[1][threadIdx.x] = s1;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) {
+      red[0][threadIdx.x] += red[0][threadIdx.x + w];
+      red[1][threadIdx.x] += red[1][threadIdx.x + w];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    out[0] = red[0][0];
+    out[1] = red[1][0];
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -496,6 +551,17 @@ int bk_rhat_partials(const double* mean, const double* m2, int64_t ld, int64_t n
   if (D == 0) return BK_OK;
   k_rhat_partials<<<dim3((unsigned)D), dim3(256), 0, bk_stream(stream)>>>(mean, m2, ld, (double)(n - 1), center,
                                                                         out, C, D);
+  BK_RETURN_LAUNCH_STATUS();
+}
+
+int bk_accept_stat(const double* lp_cur, const double* a_cur, const double* lp_prop, const double* a_prop, int64_t C,
+                   double* out, double* work, void* stream) {
+  if (!out || C < 0 || (C > 0 && (!lp_cur || !lp_prop || !work))) return BK_E_ARG;
+  const i64 nb = bk_cdiv(C, 256);
+  hipStream_t s = bk_stream(stream);
+  if (nb > 0)
+    k_accept_stat_partials<<<dim3((unsigned)nb), dim3(256), 0, s>>>(lp_cur, a_cur, lp_prop, a_prop, C, work, nb);
+  k_accept_stat_combine<<<dim3(1), dim3(256), 0, s>>>(work, nb, out);  // (C == 0: out = {0, 0})
   BK_RETURN_LAUNCH_STATUS();
 }
 

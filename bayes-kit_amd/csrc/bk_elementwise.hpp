@@ -109,8 +109,11 @@ __global__ __launch_bounds__(BLOCK) void k_traj_s(const double* th_in, double* t
 // walk is per quarter and in d order.  The momentum is read either in the state layout (rho_in) or straight from the
 // wavefront-per-chain generator's chain-major normals (zt[c*ldz + d], rho0 = 0.0 + 1.0*z as numpy's random_normal); the
 // final momentum is never stored (HMC discards it).
+// PD (a proper diagonal preconditioner, HMCDiag(precond_diag=v)): `metric` is then the packed array precond[3][D] =
+// {v, sqrt(v), 1/v}; the kicks use v[d] exactly as they use a metric, the momentum is drawn as rho0 = 0.0 + sqrt(v)[d]*z
+// and both kinetic energies are 1/2 sum rho*((1/v)[d]*rho).  The PD = false instantiations are the code they were.
 constexpr int TQ_ROWS = 8;
-template <class TERM, bool HM, bool ZT>
+template <class TERM, bool HM, bool ZT, bool PD = false>
 __global__ __launch_bounds__(BLOCK) void k_traj_q(const double* th_in, double* th_out, const double* rho_in, i64 ld,
                                                   const double* zt, i64 ldz, const double* params, const double* metric,
                                                   double eps, int steps, double* part, i64 C, i64 D) {
@@ -129,13 +132,13 @@ __global__ __launch_bounds__(BLOCK) void k_traj_q(const double* th_in, double* t
       const i64 d = (d0 + i < dhi) ? d0 + i : dhi - 1;  // rows past the end recompute the last one, unused
       dd[i] = d;
       th[i] = th_in[d * ld + c];
-      r[i] = ZT ? 0.0 + 1.0 * zt[c * ldz + d] : rho_in[d * ld + c];
+      r[i] = ZT ? 0.0 + (PD ? metric[D + d] : 1.0) * zt[c * ldz + d] : rho_in[d * ld + c];
       m[i] = HM ? metric[d] : 1.0;
     }
 #pragma unroll
     for (int i = 0; i < TQ_ROWS; ++i) {
       if (d0 + i < dhi) {
-        const double mv = HM ? m[i] * r[i] : r[i];
+        const double mv = PD ? metric[2 * D + dd[i]] * r[i] : (HM ? m[i] * r[i] : r[i]);
         k0 = k0 + r[i] * mv;
       }
       double term, g;
@@ -158,7 +161,7 @@ __global__ __launch_bounds__(BLOCK) void k_traj_q(const double* th_in, double* t
       r[i] = r[i] + half * t[i];  // hmc.py:52
       if (d0 + i < dhi) {
         th_out[(d0 + i) * ld + c] = th[i];
-        const double mv = HM ? m[i] * r[i] : r[i];
+        const double mv = PD ? metric[2 * D + dd[i]] * r[i] : (HM ? m[i] * r[i] : r[i]);  // (read here: not live in the loop)
         k1 = k1 + r[i] * mv;
         double term, g;
         TERM::eval(th[i], dd[i], params, term, g);
@@ -327,14 +330,14 @@ static int hmc_trajectory_launch(const double* theta_in, double* theta_out, cons
   BK_RETURN_LAUNCH_STATUS();
 }
 
-// Host side of bk_hmc_draw_gaussian for any separable density.
-template <class TERM>
+// Host side of bk_hmc_draw_gaussian for any separable density (PD: of bk_hmc_draw_gaussian_precond, `metric` = precond[3][D]).
+template <class TERM, bool PD = false>
 static int hmc_draw_launch(const double* theta_in, double* theta_out, int64_t ld, const double* rho_in, const double* zt,
                            int64_t ldz, const double* params, const double* metric, double eps, int64_t steps, double* part,
                            double* kin0, double* kin1, double* lp_out, double* lp_cur, const double* log_u,
                            uint8_t* accept_mask, double* ret, uint32_t* accept_count, int64_t C, int64_t D, void* stream) {
   if (!theta_in || !theta_out || (!rho_in && !zt) || (rho_in && zt) || !part || !kin1 || !lp_out || steps < 0 ||
-      steps > 0x7fffffff || C < 0 || D < 0 || (lp_cur && !log_u))
+      steps > 0x7fffffff || C < 0 || D < 0 || (lp_cur && !log_u) || (PD && !metric))
     return BK_E_ARG;
   if (ld < C || (zt && ldz < D)) return BK_E_ALIGN;
   if (C == 0 || D == 0) return BK_OK;
@@ -345,10 +348,17 @@ static int hmc_draw_launch(const double* theta_in, double* theta_out, int64_t ld
 #define BKE_TQ(HM, ZT)                                                                                              \
   k_traj_q<TERM, HM, ZT><<<grid, dim3(tq_block), 0, s>>>(theta_in, theta_out, rho_in, ld, zt, ldz, params, metric, eps, \
                                                          (int)steps, part, C, D)
-  if (metric && zt) BKE_TQ(true, true);
-  else if (metric) BKE_TQ(true, false);
-  else if (zt) BKE_TQ(false, true);
-  else BKE_TQ(false, false);
+  if constexpr (PD) {
+    if (zt) k_traj_q<TERM, true, true, true><<<grid, dim3(tq_block), 0, s>>>(theta_in, theta_out, rho_in, ld, zt, ldz, params,
+                                                                             metric, eps, (int)steps, part, C, D);
+    else k_traj_q<TERM, true, false, true><<<grid, dim3(tq_block), 0, s>>>(theta_in, theta_out, rho_in, ld, zt, ldz, params,
+                                                                           metric, eps, (int)steps, part, C, D);
+  } else {
+    if (metric && zt) BKE_TQ(true, true);
+    else if (metric) BKE_TQ(true, false);
+    else if (zt) BKE_TQ(false, true);
+    else BKE_TQ(false, false);
+  }
 #undef BKE_TQ
   k_quarter_sums<TERM><<<dim3((unsigned)bk_cdiv(C, 256)), dim3(256), 0, s>>>(part, kin0, kin1, lp_out, lp_cur, log_u,
                                                                              accept_mask, ret, accept_count, C);

@@ -256,6 +256,9 @@ struct FinishLevel {
   unsigned long long* lanes_total;
 };
 
+// KV (bk_leapfrog_finish_precond): `metric` is the packed preconditioner precond[3][D] = {v, sqrt(v), 1/v}; the kick uses
+// v[d] as it uses a metric, the kinetic energy is 1/2 sum rho*((1/v)[d]*rho).  KV = false is the code it was.
+template <bool KV>
 __global__ __launch_bounds__(RED_BLOCK) void k_finish(const double* rho_in, double* rho_out, i64 ld,
                                                       const double* grad, i64 ldg_d, i64 ldg_c,
                                                       const double* metric, double half, int negate,
@@ -291,7 +294,7 @@ __global__ __launch_bounds__(RED_BLOCK) void k_finish(const double* rho_in, doub
           double v = grad ? r[u] + half * t : r[u];  // grad NULL: kinetic energy of rho_in as is
           if (negate) v = -v;
           if (rho_out) rho_out[(d0 + u) * ld + c] = v;
-          double mv = metric ? m * v : v;
+          double mv = KV ? metric[2 * D + d0 + u] * v : (metric ? m * v : v);
           kin = kin + v * mv;
         }
     }
@@ -312,6 +315,7 @@ __global__ __launch_bounds__(RED_BLOCK) void k_finish(const double* rho_in, doub
 // The same with two chains (16 B) per lane: 128 chains per workgroup, 1 KiB per wavefront and row instead
 // of 512 B (8-byte-per-lane streams reach 0.5-0.7x the rate of 16-byte ones on gfx950: 344 us for the
 // 1.07 GB of a config-3 launch).  Each component runs the scalar kernel's operation sequence: same values.
+template <bool KV>
 __global__ __launch_bounds__(RED_BLOCK) void k_finish_v2(const double* rho_in, double* rho_out, i64 ld,
                                                          const double* grad, i64 ldg, const double* metric,
                                                          double half, int negate, double* kin_out, i64 C2, i64 D) {
@@ -347,7 +351,8 @@ __global__ __launch_bounds__(RED_BLOCK) void k_finish_v2(const double* rho_in, d
             v.y = -v.y;
           }
           if (rho_out) *reinterpret_cast<dvec2*>(rho_out + (d0 + u) * ld + 2 * c2) = v;
-          const double mx = metric ? m * v.x : v.x, my = metric ? m * v.y : v.y;
+          const double km = KV ? metric[2 * D + d0 + u] : m;
+          const double mx = metric ? km * v.x : v.x, my = metric ? km * v.y : v.y;
           kin.x = kin.x + v.x * mx;
           kin.y = kin.y + v.y * my;
         }
@@ -666,12 +671,25 @@ int bk_leapfrog_first_step_gather(const double* theta_in, const double* rho_in, 
   BK_RETURN_LAUNCH_STATUS();
 }
 
-int bk_leapfrog_finish_level(const double* rho_in, double* rho_out, int64_t ld, const double* grad, int64_t ldg_d,
-                             int64_t ldg_c, const double* metric, double half, int negate, double* kin_out,
-                             int64_t C, int64_t D, const uint32_t* n_dev, const double* logp, double* H_out,
-                             double* h_out, uint8_t* live_out, uint32_t* lanes_out, uint64_t* lanes_total,
-                             void* stream) {
-  if (!rho_in || C < 0 || D < 0) return BK_E_ARG;
+}  // extern "C"
+
+// precond[3][D] = {v, sqrt(v), 1/v}: IEEE square root and division, each correctly rounded
+__global__ __launch_bounds__(256) void k_precond_pack(const double* v, double* precond, i64 D) {
+  const i64 d = (i64)blockIdx.x * 256 + threadIdx.x;
+  if (d >= D) return;
+  const double x = v[d];
+  precond[d] = x;
+  precond[D + d] = sqrt(x);
+  precond[2 * D + d] = 1.0 / x;
+}
+
+template <bool KV>
+static int finish_level(const double* rho_in, double* rho_out, int64_t ld, const double* grad, int64_t ldg_d,
+                        int64_t ldg_c, const double* metric, double half, int negate, double* kin_out,
+                        int64_t C, int64_t D, const uint32_t* n_dev, const double* logp, double* H_out,
+                        double* h_out, uint8_t* live_out, uint32_t* lanes_out, uint64_t* lanes_total,
+                        void* stream) {
+  if (!rho_in || C < 0 || D < 0 || (KV && !metric)) return BK_E_ARG;
   if (H_out && (!logp || !h_out || !live_out || !kin_out)) return BK_E_ARG;
   if (ld < C) return BK_E_ALIGN;
   hipStream_t s = bk_stream(stream);
@@ -687,12 +705,37 @@ int bk_leapfrog_finish_level(const double* rho_in, double* rho_out, int64_t ld, 
                    (!rho_out || bk_aligned16(rho_out)) && (!kin_out || bk_aligned16(kin_out)) &&
                    (!grad || (ldg_c == 1 && ldg_d % 2 == 0 && bk_aligned16(grad)));
   if (vec)
-    k_finish_v2<<<dim3((unsigned)bk_cdiv(C / 2, BK_WAVE)), dim3(RED_BLOCK), 0, s>>>(
+    k_finish_v2<KV><<<dim3((unsigned)bk_cdiv(C / 2, BK_WAVE)), dim3(RED_BLOCK), 0, s>>>(
         rho_in, rho_out, ld, grad, ldg_d, metric, half, negate, kin_out, C / 2, D);
   else
-    k_finish<<<dim3((unsigned)bk_cdiv(C, BK_WAVE)), dim3(RED_BLOCK), 0, s>>>(
+    k_finish<KV><<<dim3((unsigned)bk_cdiv(C, BK_WAVE)), dim3(RED_BLOCK), 0, s>>>(
         rho_in, rho_out, ld, grad, ldg_d, ldg_c, metric, half, negate, kin_out, C, D, n_dev, lv);
   BK_RETURN_LAUNCH_STATUS();
+}
+
+extern "C" {
+
+int bk_leapfrog_finish_level(const double* rho_in, double* rho_out, int64_t ld, const double* grad, int64_t ldg_d,
+                             int64_t ldg_c, const double* metric, double half, int negate, double* kin_out,
+                             int64_t C, int64_t D, const uint32_t* n_dev, const double* logp, double* H_out,
+                             double* h_out, uint8_t* live_out, uint32_t* lanes_out, uint64_t* lanes_total,
+                             void* stream) {
+  return finish_level<false>(rho_in, rho_out, ld, grad, ldg_d, ldg_c, metric, half, negate, kin_out, C, D, n_dev, logp, H_out,
+                             h_out, live_out, lanes_out, lanes_total, stream);
+}
+
+int bk_precond_pack(const double* v, double* precond, int64_t D, void* stream) {
+  if (!v || !precond || D < 0) return BK_E_ARG;
+  if (D == 0) return BK_OK;
+  k_precond_pack<<<dim3((unsigned)bk_cdiv(D, 256)), dim3(256), 0, bk_stream(stream)>>>(v, precond, D);
+  BK_RETURN_LAUNCH_STATUS();
+}
+
+int bk_leapfrog_finish_precond(const double* rho_in, double* rho_out, int64_t ld, const double* grad, int64_t ldg_d,
+                               int64_t ldg_c, const double* precond, double half, int negate, double* kin_out, int64_t C,
+                               int64_t D, void* stream) {
+  return finish_level<true>(rho_in, rho_out, ld, grad, ldg_d, ldg_c, precond, half, negate, kin_out, C, D, nullptr, nullptr,
+                            nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 int bk_leapfrog_finish(const double* rho_in, double* rho_out, int64_t ld, const double* grad,

@@ -49,7 +49,9 @@ __global__ __launch_bounds__(256) void k_init_philox(uint64_t* st, i64 ldr, uint
   st[10 * ldr + c] = 4;
 }
 
-template <typename G>
+// PD (bk_momentum_refresh_precond): `metric` is the packed preconditioner precond[3][D] = {v, sqrt(v), 1/v}; the momentum is
+// 0.0 + sqrt(v)[d]*z and its kinetic energy 1/2 sum rho*((1/v)[d]*rho).  PD = false is the code it was.
+template <typename G, bool PD = false>
 __global__ __launch_bounds__(RNG_BLOCK) void k_refresh(uint64_t* st, i64 ldr, const double* loc_in,
                                                        double loc_mul, double scale, double* out,
                                                        i64 ld, const double* metric, double* kin_out,
@@ -68,10 +70,16 @@ __global__ __launch_bounds__(RNG_BLOCK) void k_refresh(uint64_t* st, i64 ldr, co
   double k0 = 0.0, k1 = 0.0, k2 = 0.0, k3 = 0.0;
   auto emit = [&](i64 d, double z) {
     double loc = loc_in ? loc_in[d * ld + c] * loc_mul : 0.0;
-    double v = loc + scale * z;  // numpy random_normal: loc + scale * z
+    double v, mv = 0.0;
+    if constexpr (PD) {  // (in a discarded branch D is not captured: the PD = false kernels keep their frame)
+      v = loc + metric[D + d] * z;
+      mv = metric[2 * D + d] * v;
+    } else {
+      v = loc + scale * z;  // numpy random_normal: loc + scale * z
+    }
     out[d * ld + c] = v;
     if (kin_out) {
-      double mv = metric ? metric[d] * v : v;
+      if constexpr (!PD) mv = metric ? metric[d] * v : v;
       double t = v * mv;
       if (d < Dq) k0 = k0 + t;
       else if (d < 2 * Dq) k1 = k1 + t;
@@ -643,7 +651,7 @@ struct DrBegin {
 
 constexpr int RK_CH = 16;  // dimensions per piece
 
-template <bool BEGIN>
+template <bool BEGIN, bool PD = false>
 __global__ __launch_bounds__(256) void k_refresh_apply_kin(const double* zt, i64 ldz, const double* loc_in,
                                                            double loc_mul, double scale, double* out, i64 ld,
                                                            const double* metric, double* kin_out, i64 C, i64 D,
@@ -679,9 +687,9 @@ __global__ __launch_bounds__(256) void k_refresh_apply_kin(const double* zt, i64
     for (int u = 0; u < RK_CH; ++u) {
       if (c < C && d0 + u < dhi) {
         double lo = loc_in ? loc[u] * loc_mul : 0.0;
-        double v = lo + scale * tile[w][lane][u];
+        double v = lo + (PD ? metric[D + d0 + u] : scale) * tile[w][lane][u];
         out[(d0 + u) * ld + c] = v;
-        double mv = metric ? metric[d0 + u] * v : v;
+        double mv = PD ? metric[2 * D + d0 + u] * v : (metric ? metric[d0 + u] * v : v);
         kin = kin + v * mv;
       }
     }
@@ -715,7 +723,7 @@ __global__ __launch_bounds__(256) void k_refresh_apply_kin(const double* zt, i64
 // 832-byte row per instruction instead of four 128-byte pieces of four rows) into ONE LDS tile with an odd row pitch, and
 // each wavefront then walks its quarter of the dimensions with lane = chain exactly as k_refresh_apply_kin does: the same
 // operations in the same order on the same values.
-template <bool BEGIN>
+template <bool BEGIN, bool PD = false>
 __global__ __launch_bounds__(256) void k_refresh_apply_kin_rows(const double* zt, i64 ldz, const double* loc_in,
                                                                 double loc_mul, double scale, double* out, i64 ld,
                                                                 const double* metric, double* kin_out, i64 C, i64 D,
@@ -751,9 +759,9 @@ __global__ __launch_bounds__(256) void k_refresh_apply_kin_rows(const double* zt
       for (int u = 0; u < 8; ++u) {
         if (d0 + u < dhi) {
           double lo = loc_in ? loc[u] * loc_mul : 0.0;
-          double v = lo + scale * rk_sm[lane * TS + (int)(d0 + u)];
+          double v = lo + (PD ? metric[D + d0 + u] : scale) * rk_sm[lane * TS + (int)(d0 + u)];
           out[(d0 + u) * ld + c] = v;
-          double mv = metric ? metric[d0 + u] * v : v;
+          double mv = PD ? metric[2 * D + d0 + u] * v : (metric ? metric[d0 + u] * v : v);
           kin = kin + v * mv;
         }
       }
@@ -782,16 +790,16 @@ __global__ __launch_bounds__(256) void k_refresh_apply_kin_rows(const double* zt
 }
 
 // launch of k_refresh_apply_kin / _rows
-template <bool BEGIN>
+template <bool BEGIN, bool PD = false>
 static void refresh_apply_kin_launch(const double* work, i64 dp, const double* loc_in, double loc_mul, double scale,
                                      double* out, i64 ld, const double* metric, double* kin_out, i64 C, i64 D,
                                      const DrBegin& b, hipStream_t s) {
   const size_t lds = (size_t)(64 * (dp + 1) + 256) * sizeof(double);
   if (dp <= 128 && lds <= 65536)
-    k_refresh_apply_kin_rows<BEGIN><<<dim3((unsigned)bk_cdiv(C, 64)), dim3(256), lds, s>>>(work, dp, loc_in, loc_mul, scale,
+    k_refresh_apply_kin_rows<BEGIN, PD><<<dim3((unsigned)bk_cdiv(C, 64)), dim3(256), lds, s>>>(work, dp, loc_in, loc_mul, scale,
                                                                                           out, ld, metric, kin_out, C, D, b);
   else
-    k_refresh_apply_kin<BEGIN><<<dim3((unsigned)bk_cdiv(C, 64)), dim3(256), 0, s>>>(work, dp, loc_in, loc_mul, scale, out,
+    k_refresh_apply_kin<BEGIN, PD><<<dim3((unsigned)bk_cdiv(C, 64)), dim3(256), 0, s>>>(work, dp, loc_in, loc_mul, scale, out,
                                                                                    ld, metric, kin_out, C, D, b);
 }
 
@@ -980,6 +988,29 @@ int bk_momentum_refresh(int rng_kind, uint64_t* state, int64_t ldr, const double
   } else if (rng_kind == BK_RNG_PCG64) {
     k_refresh<bk::Pcg64><<<grid, block, 0, s>>>(state, ldr, loc_in, loc_mul, scale, out, ld, metric, kin_out, active,
                                                 C, D);
+  } else {
+    return BK_E_ARG;
+  }
+  BK_RETURN_LAUNCH_STATUS();
+}
+
+int bk_momentum_refresh_precond(int rng_kind, uint64_t* state, int64_t ldr, double* out, int64_t ld, const double* precond,
+                                double* kin_out, int64_t C, int64_t D, double* work, int64_t work_elems, void* stream) {
+  if (!state || !out || !precond || !kin_out || C < 0 || D < 0 || ld < C || ldr < C) return BK_E_ARG;
+  if (C == 0) return BK_OK;
+  const int rb_ = rng_block(C);
+  dim3 grid((unsigned)bk_cdiv(C, rb_)), block(rb_);
+  hipStream_t s = bk_stream(stream);
+  if (rng_kind == BK_RNG_PHILOX) {
+    if (work && D >= 32 && work_elems >= bk_refresh_work_elems(C, D)) {  // (the choice bk_momentum_refresh makes)
+      i64 dp = (D + 7) / 8 * 8;
+      zig_parallel_launch(state, ldr, work, dp, C, D, nullptr, s);
+      refresh_apply_kin_launch<false, true>(work, dp, nullptr, 0.0, 1.0, out, ld, precond, kin_out, C, D, DrBegin{}, s);
+      BK_RETURN_LAUNCH_STATUS();
+    }
+    k_refresh<bk::Philox, true><<<grid, block, 0, s>>>(state, ldr, nullptr, 0.0, 1.0, out, ld, precond, kin_out, nullptr, C, D);
+  } else if (rng_kind == BK_RNG_PCG64) {
+    k_refresh<bk::Pcg64, true><<<grid, block, 0, s>>>(state, ldr, nullptr, 0.0, 1.0, out, ld, precond, kin_out, nullptr, C, D);
   } else {
     return BK_E_ARG;
   }

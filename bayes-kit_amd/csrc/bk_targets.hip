@@ -272,6 +272,21 @@ int bk_hmc_draw_gaussian(const double* theta_in, double* theta_out, int64_t ld, 
                                                 kin1, lp_out, lp_cur, log_u, accept_mask, ret, accept_count, C, D, stream);
 }
 
+int bk_hmc_draw_gaussian_precond(const double* theta_in, double* theta_out, int64_t ld, const double* rho_in,
+                                 const double* zt, int64_t ldz, const double* lam, const double* precond, double eps,
+                                 int64_t steps, double* part, double* kin0, double* kin1, double* lp_out, double* lp_cur,
+                                 const double* log_u, uint8_t* accept_mask, double* ret, uint32_t* accept_count, int64_t C,
+                                 int64_t D, void* stream) {
+  // the same kernels with the proper diagonal preconditioner precond[3][D] = {v, sqrt(v), 1/v}
+  if (lam)
+    return bke::hmc_draw_launch<GaussTerm<true>, true>(theta_in, theta_out, ld, rho_in, zt, ldz, lam, precond, eps, steps, part,
+                                                       kin0, kin1, lp_out, lp_cur, log_u, accept_mask, ret, accept_count, C, D,
+                                                       stream);
+  return bke::hmc_draw_launch<GaussTerm<false>, true>(theta_in, theta_out, ld, rho_in, zt, ldz, lam, precond, eps, steps, part,
+                                                      kin0, kin1, lp_out, lp_cur, log_u, accept_mask, ret, accept_count, C, D,
+                                                      stream);
+}
+
 int bk_mala_step_gaussian(const double* theta, double* theta_out, double* theta_prop, int64_t ld, const double* lam,
                           double* lp, const double* lp_prop, const double* log_u, const double* zt_next, int64_t ldz,
                           double eps, double sqrt2eps, uint8_t* accept_mask, double* ret, uint32_t* accept_count, int64_t C,

@@ -78,6 +78,17 @@ int bk_momentum_refresh(int rng_kind, uint64_t* state, int64_t ldr,
                         const uint8_t* active, int64_t C, int64_t D, double* work,
                         int64_t work_elems, void* stream);
 
+/* The momentum draw of HMC with a proper diagonal preconditioner (HMCDiag(precond_diag=v)).  `precond` is the packed
+ * array precond[3][D] = {v, sqrt(v), 1/v} (velocity variances, formed once per change of v); for every chain, from its
+ * stream and in the stream order of bk_momentum_refresh,
+ *     out[d][c]  = 0.0 + precond[D + d] * z_d                      rho0 = chol(diag v) z
+ *     kin_out[c] = 0.5 * sum_d out*(precond[2*D + d]*out)          1/2 rho . (M^-1 rho), the quarter order of
+ *                                                                  bk_leapfrog_finish; required
+ * in the same launches as bk_momentum_refresh (lane per chain, or wavefront per chain with `work`): no extra pass. */
+int bk_momentum_refresh_precond(int rng_kind, uint64_t* state, int64_t ldr, double* out, int64_t ld,
+                                const double* precond, double* kin_out, int64_t C, int64_t D, double* work,
+                                int64_t work_elems, void* stream);
+
 /* DRGHMC: the partial momentum refresh with its kinetic energy (bk_momentum_refresh, no mask) followed by the
  * start of the draw (bk_dr_begin_retry with kin = kin_out) -- drghmc.py:360-371.  With `work` (Philox, D >= 32) the
  * transpose of the normals into the state layout, the kinetic energy and the start of the draw are ONE launch after
@@ -166,6 +177,21 @@ int bk_leapfrog_finish(const double* rho_in, double* rho_out, int64_t ld,
                        const double* grad, int64_t ldg_d, int64_t ldg_c,
                        const double* metric, double half, int negate,
                        double* kin_out, int64_t C, int64_t D, void* stream);
+
+/* The packed form of a diagonal preconditioner from its D velocity variances v (finite, positive: the caller checks):
+ *     precond[d] = v[d]     precond[D + d] = sqrt(v[d])     precond[2*D + d] = 1.0 / v[d]
+ * square root and division correctly rounded (IEEE 754), so a host restatement has the same doubles.  v may be the first
+ * row of precond. */
+int bk_precond_pack(const double* v, double* precond, int64_t D, void* stream);
+
+/* The same for a proper diagonal preconditioner, precond[3][D] = {v, sqrt(v), 1/v}: the kick vector and the
+ * kinetic-energy vector differ,
+ *     r = rho_in + half * (precond[d] * grad)
+ *     kin_out[c] = 0.5 * sum_d r*(precond[2*D + d]*r)
+ * everything else (negate, rho_out, grad NULL, the order of the sums) as above. */
+int bk_leapfrog_finish_precond(const double* rho_in, double* rho_out, int64_t ld, const double* grad, int64_t ldg_d,
+                               int64_t ldg_c, const double* precond, double half, int negate, double* kin_out,
+                               int64_t C, int64_t D, void* stream);
 
 /* ---- the same three steps over a lane set whose SIZE LIVES ON THE DEVICE -----------------------
  * (drghmc.py:276-278, :280-283, :285-286 for the chains that reach a delayed-rejection proposal or one
@@ -519,6 +545,18 @@ int bk_hmc_draw_gaussian(const double* theta_in, double* theta_out, int64_t ld, 
                          double* lp_out, double* lp_cur, const double* log_u, uint8_t* accept_mask,
                          double* ret, uint32_t* accept_count, int64_t C, int64_t D, void* stream);
 
+/* bk_hmc_draw_gaussian with a proper diagonal preconditioner, precond[3][D] = {v, sqrt(v), 1/v} (required): the
+ * trajectory kicks with precond[d] exactly as with a metric; chain-major normals become rho0 = 0.0 + precond[D + d]*z
+ * (rho_in is taken as stored: bk_momentum_refresh_precond has scaled it), and
+ *     kin0[c] = 0.5 * sum_d rho0*(precond[2*D + d]*rho0)      kin1[c] = 0.5 * sum_d rho1*(precond[2*D + d]*rho1)
+ * in the same quarter order: bit-identical to bk_momentum_refresh_precond, the step-by-step trajectory with
+ * metric = precond (its first D entries) and bk_leapfrog_finish_precond.  Every other argument as above. */
+int bk_hmc_draw_gaussian_precond(const double* theta_in, double* theta_out, int64_t ld, const double* rho_in,
+                                 const double* zt, int64_t ldz, const double* lam, const double* precond, double eps,
+                                 int64_t steps, double* part, double* kin0, double* kin1, double* lp_out,
+                                 double* lp_cur, const double* log_u, uint8_t* accept_mask, double* ret,
+                                 uint32_t* accept_count, int64_t C, int64_t D, void* stream);
+
 /* bk_mala_step for a SEPARABLE built-in density (the Gaussians: lam NULL = identity): proposal densities, accept, select and
  * the next draw's proposal (bayes_kit/mala.py:41-66) with both gradients RECOMPUTED from theta / theta_prop where bk_mala_step
  * loads them, and the gradient at the new state never stored -- 56*D bytes per chain-draw with the log-density launch
@@ -724,6 +762,17 @@ int bk_record_series_dev(const double* theta, int64_t ld, const int32_t* dims, i
  * np.var(means, ddof=1)).  Deterministic fixed-shape tree per dimension. */
 int bk_rhat_partials(const double* mean, const double* m2, int64_t ld, int64_t n,
                      const double* center, double* out, int64_t C, int64_t D, void* stream);
+
+/* The acceptance statistic a step-size adaptation averages, before the accept test overwrites lp_cur:
+ *     d_c    = (lp_prop[c] - a_prop[c]) - (lp_cur[c] - a_cur[c])      the h1 - h0 of bk_mh_accept in HMC mode
+ *     out[0] = sum_c min(1, bk_exp(min(0, d_c)))   over the chains whose d_c is not NaN
+ *     out[1] = number of chains whose d_c is NaN
+ * a_cur / a_prop NULL = zeros.  bk_exp is include/bkhip_math.h's: the same double on host and device.  The sums are a
+ * fixed-shape tree -- 64 chains by the xor butterfly (strides 1, 2, .. 32), four such as ((w0+w1)+w2)+w3 per 256 chains
+ * into work, then thread t of ONE workgroup adds partials t, t+256, .. in order and the 256 sums are halved 128, 64, .. 1
+ * -- so the bits depend on C only.  work: caller scratch of 2*ceil(C/256) doubles.  C = 0: out = {0, 0}. */
+int bk_accept_stat(const double* lp_cur, const double* a_cur, const double* lp_prop, const double* a_prop, int64_t C,
+                   double* out, double* work, void* stream);
 
 /* Per-chain mean and ddof=1 variance of a stored series x[t*ld + c], t < len[c] (len NULL =
  * all N): the two list comprehensions of rhat.py:165-166 for ragged chains. */

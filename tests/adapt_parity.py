@@ -1,0 +1,176 @@
+"""Checks of the diagonal preconditioner (HMCDiag(precond_diag=v)), the adaptation statistics and HMCDiag.warmup that
+take the kernel library as an argument: tests/test_adapt_cpu.py runs them on the NumPy stand-in (tests/fake_ops_adapt.py),
+tests/test_gpu_adapt.py on the HIP library."""
+import numpy as np
+import torch
+
+import bayes_kit_amd as bk
+
+PATHS = ("auto", "step", "opaque")
+
+
+def _np(t):
+    return np.asarray(t.cpu())
+
+
+def perturbed_variances(lam, seed=5):
+    """1/lam perturbed by +-30 %: a useful but imperfect preconditioner."""
+    g = np.random.default_rng(seed)
+    return (1.0 / lam) * (1.0 + 0.3 * (2.0 * g.random(lam.shape[0]) - 1.0))
+
+
+def run_draws(s, n):
+    th, lp = [], []
+    for _ in range(n):
+        t, l = s.sample()
+        th.append(_np(t).copy())
+        lp.append(_np(l).copy())
+    return np.stack(th), np.stack(lp)
+
+
+def check_precond_vs_oracle(ops, C, D, path, draws=6, rtol=1e-10):
+    """Against the independent specification: oracle.samplers.HMCDense with M = diag(v), the tolerances of
+    check_dense_metric_hmc (the oracle takes M @ g and the kinetic energy with a D x D product: another summation order)."""
+    from oracle import models as om
+    from oracle import samplers as osamp
+
+    lam = np.logspace(0, 1, D)
+    v = perturbed_variances(lam)
+    s = bk.HMCDiag(bk.DiagGaussian(lam, ops=ops), 0.05, 7, chains=C, seed=31, precond_diag=v, path=path, ops=ops)
+    th, lp = run_draws(s, draws)
+    for c in range(0, C, max(1, C // 8)):
+        o = osamp.HMCDense(om.DiagGaussian(lam), 0.05, 7, np.diag(v), seed=np.random.Philox(key=[31, c]))
+        for n in range(draws):
+            oth, olp = o.sample()
+            np.testing.assert_allclose(th[n][c], oth, rtol=rtol, atol=1e-13)
+            np.testing.assert_allclose(lp[n][c], olp, rtol=rtol, atol=1e-12)
+    assert 0.3 < s.accept_rate() <= 1.0
+
+
+def _six_draws(ops, C, D, path, v, v2=None, **kw):
+    """6 draws; v2: set_precond_diag(v2) between draws 3 and 4."""
+    lam = np.logspace(0, 1, D)
+    s = bk.HMCDiag(bk.DiagGaussian(lam, ops=ops), 0.05, 7, chains=C, seed=77, precond_diag=v, path=path, ops=ops, **kw)
+    th, _ = run_draws(s, 3)
+    if v2 is not None:
+        s.set_precond_diag(v2)
+    th2, _ = run_draws(s, 3)
+    return np.concatenate([th, th2]), s.rng_state().copy()
+
+
+def check_paths_agree(ops, C, D, knobs_list):
+    """The three paths give array_equal draws and equal final stream positions, whatever the knobs, with the
+    preconditioner replaced between draws 3 and 4 and without."""
+    lam = np.logspace(0, 1, D)
+    v = perturbed_variances(lam)
+    v2 = perturbed_variances(lam, seed=6)
+    for change in (None, v2):
+        ref_th, ref_rng = _six_draws(ops, C, D, "opaque", v, change)
+        for knobs in knobs_list:
+            for path in PATHS:
+                th, rng = _six_draws(ops, C, D, path, v, change, **knobs)
+                assert np.array_equal(th, ref_th), (path, knobs, change is not None)
+                assert np.array_equal(rng, ref_rng), (path, knobs, change is not None)
+
+
+def check_identity(ops, C, D):
+    """precond_diag = ones IS the sampler without it: multiplying by 1.0 is exact."""
+    lam = np.logspace(0, 1, D)
+    for path in PATHS:
+        a = bk.HMCDiag(bk.DiagGaussian(lam, ops=ops), 0.05, 7, chains=C, seed=3, precond_diag=np.ones(D), path=path, ops=ops)
+        b = bk.HMCDiag(bk.DiagGaussian(lam, ops=ops), 0.05, 7, chains=C, seed=3, path=path, ops=ops)
+        ta, _ = run_draws(a, 4)
+        tb, _ = run_draws(b, 4)
+        assert np.array_equal(ta, tb), path
+        assert np.array_equal(a.rng_state(), b.rng_state()), path
+
+
+def check_checkpoint(ops, C, D, path):
+    """state_dict after draw 3 (preconditioner and a changed step size inside), load into a fresh sampler built with
+    neither, draws 4-6 array_equal."""
+    lam = np.logspace(0, 1, D)
+    v = perturbed_variances(lam)
+    a = bk.HMCDiag(bk.DiagGaussian(lam, ops=ops), 0.05, 7, chains=C, seed=9, precond_diag=v, path=path, ops=ops)
+    run_draws(a, 3)
+    a._stepsize = 0.04
+    sd = a.state_dict()
+    ta, la = run_draws(a, 3)
+    b = bk.HMCDiag(bk.DiagGaussian(lam, ops=ops), 0.05, 7, chains=C, seed=1234, path=path, ops=ops)
+    b.load_state_dict(sd)
+    assert b._stepsize == 0.04 and np.array_equal(b.precond_diag, v)
+    tb, lb = run_draws(b, 3)
+    assert np.array_equal(ta, tb) and np.array_equal(la, lb)
+
+
+def precond_driver(ops, C, D, path="auto"):
+    """The same Python driver for the stand-in and the real ops (GPU vs NumPy restatement)."""
+    lam = np.logspace(0, 1, D)
+    s = bk.HMCDiag(bk.DiagGaussian(lam, ops=ops), 0.05, 7, chains=C, seed=55, precond_diag=perturbed_variances(lam), path=path,
+                   ops=ops)
+    return run_draws(s, 4)
+
+
+def check_pooled_variance(ops, C=37, D=5, n=23):
+    """RunningMoments.pooled_variance against the formula on the stored draws, rel 1e-12 (and reset())."""
+    g = np.random.default_rng(8)
+    x = g.normal(size=(n, D, C)) * np.arange(1, D + 1)[None, :, None] + g.normal(size=(1, D, C))
+    rm = bk.RunningMoments(D, C, ops=ops)
+    for t in range(n):
+        rm.update(torch.from_numpy(x[t]).to(ops.device), layout="dc")
+    want = (n - 1) / n * x.var(axis=0, ddof=1).mean(axis=1) + x.mean(axis=0).var(axis=1, ddof=1)
+    got = rm.pooled_variance()
+    np.testing.assert_allclose(got, want, rtol=1e-12)
+    # ... which is np.var of the pooled draws up to the ddof convention: (n C - 1) / (n C) sits between the two
+    pooled = np.moveaxis(x, 1, 0).reshape(D, -1).var(axis=1, ddof=1)
+    np.testing.assert_allclose(got, pooled, rtol=2.0 / C)
+    rm.reset()
+    assert rm.n == 0 and not _np(rm.mean).any() and not _np(rm.m2).any()
+    for t in range(2):
+        rm.update(torch.from_numpy(x[t]).to(ops.device), layout="dc")
+    want2 = 0.5 * x[:2].var(axis=0, ddof=1).mean(axis=1) + x[:2].mean(axis=0).var(axis=1, ddof=1)
+    np.testing.assert_allclose(rm.pooled_variance(), want2, rtol=1e-12)
+
+
+def accept_stat_inputs(C, seed=0):
+    """Random energies with planted NaN, +inf, -inf and d > 0 cases."""
+    g = np.random.default_rng(seed + C)
+    lp0, a0, lp1, a1 = (g.normal(size=C) * s for s in (3.0, 2.0, 3.0, 2.0))
+    a0, a1 = np.abs(a0), np.abs(a1)
+    if C >= 1:
+        lp1[0] = lp0[0] + 5.0 + (a1[0] - a0[0])  # d > 0: counts 1
+    if C >= 8:
+        lp1[3] = np.nan
+        lp1[5] = np.inf    # d = +inf: counts 1
+        lp1[6] = -np.inf   # d = -inf: counts 0
+        lp0[7], lp1[7] = np.inf, np.inf  # inf - inf: NaN
+    if C >= 64:
+        lp1[C - 1] = np.nan
+        lp1[C // 2] = -800.0  # underflow of exp
+    return lp0, a0, lp1, a1
+
+
+def run_warmup(ops, seed, path="auto", draws=300, C=512, **kw):
+    lam = np.logspace(0, 4, 32)
+    s = bk.HMCDiag(bk.DiagGaussian(lam, ops=ops), 0.006, 16, chains=C, seed=seed, path=path, ops=ops, **kw)
+    return s, s.warmup(draws), lam
+
+
+def check_warmup_report(rep, lam, draws=300):
+    """The issue's end-to-end conditions (prototype's range over eight seeds in brackets):
+    max_d |v_d lam_d - 1| <= 0.10 [0.021-0.036]; final eps >= 0.3 [0.66-0.74]; mean alpha of the last 20 draws in
+    [0.70, 0.90] [0.78-0.82]."""
+    v = rep["precond_diag"]
+    dev = float(np.abs(v * lam - 1.0).max())
+    last = float(np.mean(rep["alpha"][-20:]))
+    print(f"warmup: max|v lam - 1| = {dev:.4f}  eps = {rep['stepsize']:.4f}  mean alpha (last 20) = {last:.4f}  "
+          f"nan_chains = {rep['nan_chains']}")
+    assert len(rep["eps"]) == draws and len(rep["alpha"]) == draws and rep["eps"][0] == 0.006
+    assert rep["window_ends"] == [100, 150, 250] and rep["nan_chains"] == 0
+    assert dev <= 0.10
+    assert rep["stepsize"] >= 0.3
+    assert 0.70 <= last <= 0.90
+
+
+def reports_equal(a, b):
+    return (a["stepsize"] == b["stepsize"] and np.array_equal(a["precond_diag"], b["precond_diag"]) and a["eps"] == b["eps"]
+            and a["alpha"] == b["alpha"] and a["window_ends"] == b["window_ends"] and a["nan_chains"] == b["nan_chains"])
