@@ -725,8 +725,8 @@ class Ops:
 
     def dense_metric_apply(self, M, X, Y):
         D, C = X.shape
-        assert _ld(Y) == _ld(X) and M.stride(1) == 1
-        self._call("bk_dense_metric_apply", ptr(M), M.stride(0), ptr(X), ptr(Y), _ld(X), C, D, self._s())
+        assert _ld(Y) == _ld(X)
+        self._call("bk_dense_metric_apply", ptr(M), _ld(M), ptr(X), ptr(Y), _ld(X), C, D, self._s())
 
     def gemm_chains_work(self, R, K, C):
         """Split-K scratch for gemm_chains (a tensor of bk_gemm_chains_work_elems doubles, or None: no split)."""
@@ -736,15 +736,16 @@ class Ops:
     def gemm_chains(self, A, X, Y, work=None):
         """Y[R, C] = A[R, K] @ X[K, C] on the fp64 matrix cores (work: optional split-K scratch)."""
         R, K = A.shape
-        assert X.shape[0] == K and Y.shape[0] == R and A.stride(1) == 1
-        self._call("bk_gemm_chains", ptr(A), A.stride(0), R, K, ptr(X), _ld(X), ptr(Y), _ld(Y), X.shape[1],
+        assert X.shape[0] == K and Y.shape[0] == R
+        # (_ld: the stride of a one-row A says nothing -- torch leaves it at 1 for the transpose of an [N, 1] design matrix)
+        self._call("bk_gemm_chains", ptr(A), _ld(A), R, K, ptr(X), _ld(X), ptr(Y), _ld(Y), X.shape[1],
                    ptr(work), 0 if work is None else work.numel(), self._s())
 
     def gemm_chains_logistic(self, A, X, Y, y_rows):
         """Y[R, C] = y_rows[:, None] - sigmoid(A[R, K] @ X[K, C]): gemm_chains + logistic_residual(part=None) in one launch."""
         R, K = A.shape
-        assert X.shape[0] == K and Y.shape[0] == R and A.stride(1) == 1 and y_rows.numel() == R
-        self._call("bk_gemm_chains_logistic", ptr(A), A.stride(0), R, K, ptr(X), _ld(X), ptr(Y), _ld(Y), X.shape[1],
+        assert X.shape[0] == K and Y.shape[0] == R and y_rows.numel() == R
+        self._call("bk_gemm_chains_logistic", ptr(A), _ld(A), R, K, ptr(X), _ld(X), ptr(Y), _ld(Y), X.shape[1],
                    ptr(y_rows), self._s())
 
     def logistic_residual(self, Z, y, part, segments=None):

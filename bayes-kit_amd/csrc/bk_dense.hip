@@ -235,8 +235,10 @@ static int gemm_block(const double* A, i64 lda, i64 R, i64 K, const double* X, i
   i64 rb = bk_cdiv(R, BM), cb = bk_cdiv(C, BN);
   i64 per = (cb + 7) / 8;
   if (per * 8 * rb > 0x7fffffff) return BK_E_ARG;
-  const bool full_but_rows = (K % BK == 0) && (C % BN == 0) && (lda % 2 == 0) && (ldx % 2 == 0) && bk_aligned16(A) &&
-                             bk_aligned16(X);
+  // (K = 0 is an empty sum, Y = 0: the unchecked kernel loads its first panels before it looks at the panel count,
+  // which on a zero-width A or X is a read past the buffer, so that case takes the checked kernel)
+  const bool full_but_rows = (K > 0) && (K % BK == 0) && (C % BN == 0) && (lda % 2 == 0) && (ldx % 2 == 0) &&
+                             bk_aligned16(A) && bk_aligned16(X);
   hipStream_t st = bk_stream(stream);
   // Whole 128-row blocks take the unchecked kernel; a last partial block of rows (R = 10^6 observations: 64 rows)
   // is a second, small launch of the checked one instead of putting bounds checks into every tile of the first.

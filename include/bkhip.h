@@ -682,7 +682,9 @@ int bk_dense_metric_apply(const double* M, int64_t ldm, const double* X, double*
  * slabs are summed in a fixed order.  The split is a function of (R, K) only and calls wider than 2,048
  * chains are cut into column blocks: a chain's result does not depend on how many chains share its call
  * (chains sharded over GPUs reproduce the unsharded run bit for bit).  A `work` that is too small is
- * refused (BK_E_ARG), never answered with another split. */
+ * refused (BK_E_ARG), never answered with another split.  R = 0 or C = 0 returns without touching Y; K = 0 is the
+ * empty sum: Y = 0 (bk_gemm_chains_logistic: y_rows[r] - 0.5), and A and X are not read.  A NULL A, X or Y is
+ * BK_E_ARG at any size. */
 int64_t bk_gemm_chains_work_elems(int64_t R, int64_t K, int64_t C);
 int bk_gemm_chains(const double* A, int64_t lda, int64_t R, int64_t K, const double* X, int64_t ldx,
                    double* Y, int64_t ldy, int64_t C, double* work, int64_t work_elems, void* stream);

@@ -466,42 +466,75 @@ class FakeOps:
         if level is not None:
             self.dr_level_begin(lvl_logp, lvl_kin, level[0], level[1], level[2], n)
 
+    @staticmethod
+    def _gemm(A, X, Y):
+        # gemm_launch of csrc/bk_dense.hip: a null pointer is BK_E_ARG at any size; R = 0 or C = 0 touches nothing;
+        # K = 0 is the empty sum
+        if 0 in (A.data_ptr(), X.data_ptr(), Y.data_ptr()):
+            raise _lib.BkHipError("bk_gemm_chains failed: BK_E_ARG")
+        if Y.shape[0] == 0 or Y.shape[1] == 0:
+            return False
+        # rank-one updates in increasing k, not BLAS: a column's sum must not depend on the columns next to it (the
+        # library's promise for chains that share a launch), and a BLAS picks its blocking by the width of the call
+        a, x = A.numpy(), X.numpy()
+        acc = np.zeros(Y.shape)
+        for k in range(a.shape[1]):
+            acc += a[:, k, None] * x[k, None, :]
+        Y.numpy()[...] = acc
+        return True
+
     def dense_metric_apply(self, M, X, Y):
-        Y.numpy()[...] = M.numpy() @ X.numpy()
+        self._gemm(M, X, Y)
 
     def gemm_chains_work(self, R, K, C):
         return None
 
     def gemm_chains(self, A, X, Y, work=None):
-        Y.numpy()[...] = A.numpy() @ X.numpy()
+        self._gemm(A, X, Y)
 
     def gemm_chains_logistic(self, A, X, Y, y_rows):
-        self.gemm_chains(A, X, Y)
-        self.logistic_residual(Y, y_rows, None)
+        if self._gemm(A, X, Y):
+            self.logistic_residual(Y, y_rows, None)
 
     def logistic_residual(self, Z, y, part, segments=None):
+        # k_logistic_residual's arithmetic: one exp(-|z|), softplus = max(z, 0) + log1p(e), sigmoid by the sign of z;
+        # segment s holds rows [s * rows, (s + 1) * rows) with rows = ceil(max(N, 1) / segments), summed in row order
         z = Z.numpy()
+        N = z.shape[0]
         yv = y.numpy()[:, None]
-        if part is not None:
-            S = part.shape[0]
-            N = z.shape[0]
-            rows = -(-max(N, 1) // S)
-            ll = yv * z - np.logaddexp(0.0, z)
-            for s in range(S):
-                part.numpy()[s] = ll[s * rows:(s + 1) * rows].sum(axis=0)
-        from scipy.special import expit
-
-        z[...] = yv - expit(z)
+        with np.errstate(all="ignore"):
+            e = np.exp(-np.abs(z))
+            if part is not None:
+                S = part.shape[0]
+                rows = -(-max(N, 1) // S)
+                ll = yv * z - (np.where(z > 0.0, z, 0.0) + np.log1p(e))
+                p = part.numpy()
+                p[...] = 0.0
+                for s in range(min(S, -(-N // rows))):
+                    acc = np.zeros(z.shape[1])
+                    for row in ll[s * rows:(s + 1) * rows]:
+                        acc = acc + row
+                    p[s] = acc
+            z[...] = yv - np.where(z >= 0.0, 1.0 / (1.0 + e), e / (1.0 + e))
 
     def logistic_finish(self, G, theta, part, inv_prior_var, t, grad, logp, loglik):
+        if (part is None and (logp is not None or loglik is not None)) or (grad is not None and G is None):
+            raise _lib.BkHipError("bk_logistic_finish failed: BK_E_ARG")
         th = theta.numpy()
-        ll = None if part is None else part.numpy().sum(axis=0)
+        ll = None
+        if part is not None:
+            ll = np.zeros(th.shape[1])
+            for row in part.numpy():  # left to right
+                ll = ll + row
         if grad is not None:
             grad.numpy()[...] = t * G.numpy() + (-(inv_prior_var * th))
         if loglik is not None:
             loglik.numpy()[...] = ll
         if logp is not None:
-            logp.numpy()[...] = t * ll + (-0.5 * inv_prior_var * (th * th).sum(axis=0))
+            s2 = np.zeros(th.shape[1])
+            for row in th:  # in row order, like the kernel
+                s2 = s2 + row * row
+            logp.numpy()[...] = t * ll + (-0.5 * inv_prior_var * s2)
 
     def dot_columns(self, x, y, scale, out):
         out.numpy()[...] = scale * np.einsum("dc,dc->c", x.numpy(), y.numpy())

@@ -43,7 +43,62 @@ def make_model(spec):
         from test.models.binomial import Binomial
 
         return Binomial(alpha=2, beta=3, x=5, N=15)
+    if kind == "logistic":
+        return make_logistic(spec)[0]
     raise KeyError(kind)
+
+
+def make_logistic(spec, long_double=False):
+    """(model, SHA-256 of the data): oracle.models.LogisticRegression on data regenerated from default_rng(data_seed)
+    (tests/helpers.logistic_data) -- user code from the reference's view, like every other model here.  long_double:
+    the same density through tests/logistic_ref.py, the perturbed model of the conditions below."""
+    from tests.helpers import logistic_data, logistic_sha256
+
+    X, y = logistic_data(spec)
+    if long_double:
+        from tests.logistic_ref import LongDoubleLogistic
+
+        return LongDoubleLogistic(X, y, prior_scale=spec["prior_scale"]), logistic_sha256(X, y)
+    return models.LogisticRegression(X, y, prior_scale=spec["prior_scale"]), logistic_sha256(X, y)
+
+
+def deviation(got, want, floor=None):
+    """max |got - want| / |want|  (floor: |want| is taken as at least `floor`, for coordinates near zero)."""
+    den = np.abs(want) if floor is None else np.maximum(np.abs(want), floor)
+    return float(np.max(np.abs(got - want) / den))
+
+
+THETA_FLOOR = 1e-3  # theta: relative error, absolute below |theta| = 1e-3 (an absolute floor of 1e-3 * tol)
+
+
+def logistic_sampler_conditions(case, res):
+    """The conditions under which a rounding-level difference in the density cannot legitimately flip a decision of a
+    logistic fixture -- asserted, not measured (a seed that fails one is replaced):
+      * every stored chain accepts at least 3 times and rejects at least 3 times;
+      * the oracle sampler rerun with the long-double model makes the same accept decisions and ends on the same stream
+        state.
+    tol = 100 x the largest deviation between the fixture and that rerun over all draws (theta: relative with the floor
+    above; logp: relative), the factor for a device's different summation order; it must be <= 1e-9."""
+    from tests.helpers import oracle_sampler
+
+    N, C, D = res["draws"].shape
+    acc = res["accepted"]
+    assert np.all(acc.sum(axis=0) >= 3) and np.all((~acc).sum(axis=0) >= 3), (case["name"], acc.sum(axis=0))
+    model = make_logistic(case["model"], long_double=True)[0]
+    dev = 0.0
+    for j, c in enumerate(case["chain_ids"]):
+        s = oracle_sampler(case, c, model=model)
+        prev = np.array(s._theta, dtype=np.float64)
+        assert np.array_equal(prev, res["theta0"][j])
+        for n in range(N):
+            th, lp = s.sample()
+            assert bool(np.any(th != prev)) == bool(acc[n, j]), (case["name"], c, n, "decision flips under rounding")
+            prev = np.array(th, dtype=np.float64)
+            dev = max(dev, deviation(th, res["draws"][n, j], THETA_FLOOR), deviation(lp, res["logp"][n, j]))
+        assert np.array_equal(rng_state(s._rng), res["rng_state"][j]), (case["name"], c)
+    tol = 100.0 * dev
+    assert 0.0 < tol <= 1e-9, (case["name"], tol)
+    return tol
 
 
 def make_metric(spec, D):
@@ -112,18 +167,22 @@ def run_sampler_case(case):
     C, N = case["chains"], case["draws"]
     model0 = make_model(case["model"])
     D = model0.dims()
+    logistic = case["model"]["kind"] == "logistic"
+    ids = case.get("chain_ids", list(range(C)))  # the chain index in the Philox key of every stored chain
+    assert len(ids) == C
+    accepted = np.zeros((N, C), dtype=bool)
     draws = np.empty((N, C, D))
     logps = np.empty((N, C))
     grad_calls = np.zeros((N, C), dtype=np.int64)
     theta0 = np.empty((C, D))
     states = []
     rho_final = np.zeros((C, D))
-    for c in range(C):
-        model = CountingModel(make_model(case["model"]))
+    for c, chain_id in enumerate(ids):
+        model = CountingModel(model0 if logistic else make_model(case["model"]))
         if "pcg_seed" in case:
-            seed = case["pcg_seed"] + c
+            seed = case["pcg_seed"] + chain_id
         else:
-            seed = np.random.Philox(key=[case["seed"], c])
+            seed = np.random.Philox(key=[case["seed"], chain_id])
         init = None
         if case.get("init") is not None:
             init = np.asarray(case["init"], dtype=np.float64).copy()
@@ -144,7 +203,7 @@ def run_sampler_case(case):
                 prob_retry=case.get("prob_retry", True),
             )
         elif alg in ("metropolis", "mh"):
-            proposal_fn, transition_lp_fn = make_proposal(case["proposal"], c)
+            proposal_fn, transition_lp_fn = make_proposal(case["proposal"], chain_id)
             if alg == "metropolis":
                 s = ref.Metropolis(model, proposal_fn, init=init, seed=seed)
             else:
@@ -155,16 +214,19 @@ def run_sampler_case(case):
         if metric is not None:
             s._metric = metric  # the reference cannot take a D>1 metric in its constructor
         theta0[c] = np.asarray(s._theta, dtype=np.float64)
+        prev = theta0[c].copy()
         for n in range(N):
             before = model.grad_calls
             th, lp = s.sample()
+            accepted[n, c] = bool(np.any(np.asarray(th) != prev))
+            prev = np.array(th, dtype=np.float64)
             draws[n, c] = th
             logps[n, c] = lp
             grad_calls[n, c] = model.grad_calls - before
         states.append(rng_state(s._rng))
         if alg == "drghmc":
             rho_final[c] = s._rho
-    return dict(
+    res = dict(
         case=np.array(json.dumps(case)),
         theta0=theta0,
         draws=draws,
@@ -173,7 +235,14 @@ def run_sampler_case(case):
         rng_state=np.stack(states),
         rho_final=rho_final,
     )
+    if logistic:
+        res.update(accepted=accepted, chain_ids=np.asarray(ids, dtype=np.int64),
+                   data_sha256=np.array(make_logistic(case["model"])[1]))
+        res["tol"] = np.float64(logistic_sampler_conditions(case, res))
+    return res
 
+
+LOGISTIC_CHAIN_IDS = [0, 1, 63, 64, 65, 127, 128, 129]
 
 SAMPLER_CASES = [
     # --- HMC (bayes_kit/hmc.py) ---
@@ -274,6 +343,17 @@ SAMPLER_CASES = [
     # HMC: one leapfrog step with a non-trivial metric
     dict(name="hmc_diag40_metric_steps1", alg="hmc", model=dict(kind="diag_gaussian", D=40, log10_lo=0, log10_hi=1),
          stepsize=0.1, steps=1, chains=4, draws=40, seed=105, metric=dict(kind="linspace", lo=0.6, hi=1.3)),
+    # --- the logistic-regression target (two GEMMs per gradient in the HIP library): eight chains whose ids lie on both
+    # sides of a wavefront and of a 128-chain tile; N = 2100, D = 40 is a partial row block with K % 16 != 0 in both GEMMs.
+    # Step sizes chosen for 70-90 % acceptance on this data (logistic_sampler_conditions asserts what the seeds must give)
+    dict(name="hmc_logistic16", alg="hmc", model=dict(kind="logistic", N=1536, D=16, data_seed=51, prior_scale=2.0),
+         stepsize=0.2, steps=8, chains=8, chain_ids=LOGISTIC_CHAIN_IDS, draws=30, seed=601),
+    dict(name="hmc_logistic40", alg="hmc", model=dict(kind="logistic", N=2100, D=40, data_seed=52, prior_scale=2.0),
+         stepsize=0.25, steps=8, chains=8, chain_ids=LOGISTIC_CHAIN_IDS, draws=30, seed=603),
+    dict(name="mala_logistic16", alg="mala", model=dict(kind="logistic", N=1536, D=16, data_seed=51, prior_scale=2.0),
+         epsilon=0.02, chains=8, chain_ids=LOGISTIC_CHAIN_IDS, draws=30, seed=600),
+    dict(name="mala_logistic40", alg="mala", model=dict(kind="logistic", N=2100, D=40, data_seed=52, prior_scale=2.0),
+         epsilon=0.03, chains=8, chain_ids=LOGISTIC_CHAIN_IDS, draws=30, seed=600),
 ]
 
 
@@ -286,7 +366,46 @@ def make_smc_model(spec):
         g = np.random.default_rng(spec["data_seed"])
         D = spec["D"]
         return models.GaussPriorLik(y=g.normal(size=D) * 1.5, prec=np.logspace(0, 1.5, D), prior_scale=spec["prior_scale"])
+    if spec["kind"] == "logistic":
+        return make_logistic(spec)[0]
     raise KeyError(spec)
+
+
+def logistic_smc_conditions(case, res):
+    """As logistic_sampler_conditions, for the SMC fixture: the oracle's SMC rerun on the same stream with the long-double
+    model moves the same particles, draws the same ancestor indices and ends on the same stream position; and no
+    resampling uniform lies within 1e-9 of a boundary of the cdf it is searched in."""
+    from oracle import smc as osmc
+
+    M, N = case["M"], case["N"]
+    finals = []
+    dev = 0.0
+    for long_double in (False, True):
+        model = make_logistic(case["model"], long_double)[0]
+        rs = np.random.RandomState(case["seed"])
+        stream = osmc.NumpyLegacySource(rs)
+        o = osmc.TemperedLikelihoodSMC(model, M, N, lambda i: res["theta0"][i], osmc.metropolis_kernel(case["scale"], stream),
+                                       stream)
+        for n in range(1, N + 1):
+            before = o.thetas.copy()
+            o.transition(n)
+            assert np.array_equal(o.idxs, res["idx"][n - 1]), (n, long_double)
+            assert np.array_equal(np.any(o.moved != before, axis=1), np.any(res["moved"][n - 1] != before, axis=1)), n
+            if not long_double:
+                assert np.array_equal(o.moved, res["moved"][n - 1]), n
+                cdf = np.cumsum(o.weights / o.weights.sum())
+                cdf /= cdf[-1]
+                gap = np.abs(res["choice_uniforms"][n - 1][:, None] - cdf[None, :]).min()
+                assert gap > 1e-9, (n, gap)
+            else:
+                dev = max(dev, deviation(o.moved, res["moved"][n - 1], THETA_FLOOR))
+        st = rs.get_state(legacy=False)
+        finals.append((int(st["state"]["pos"]), int(st["has_gauss"]), st["state"]["key"][:8].copy()))
+    for f in finals:
+        assert f[0] == int(res["final_pos"]) and f[1] == int(res["final_has_gauss"]) and np.array_equal(f[2], res["final_key"])
+    tol = 100.0 * dev
+    assert tol <= 1e-9, tol
+    return tol
 
 
 def smc_initial(case, model):
@@ -372,10 +491,14 @@ def run_smc_case(case):
         cur = after[n].copy()
     final_state = np.random.get_state(legacy=False)
     # (the particles after resampling are moved[n][idx[n]] -- checked above -- and are not stored twice)
-    return dict(case=np.array(json.dumps(case)), theta0=theta0, moved=moved, idx=idx,
-                normals=z_exact, uniforms=u, choice_uniforms=cu,
-                final_pos=np.int64(final_state["state"]["pos"]), final_key=final_state["state"]["key"][:8].copy(),
-                final_has_gauss=np.int64(final_state["has_gauss"]))
+    res = dict(case=np.array(json.dumps(case)), theta0=theta0, moved=moved, idx=idx,
+               normals=z_exact, uniforms=u, choice_uniforms=cu,
+               final_pos=np.int64(final_state["state"]["pos"]), final_key=final_state["state"]["key"][:8].copy(),
+               final_has_gauss=np.int64(final_state["has_gauss"]))
+    if case["model"]["kind"] == "logistic":
+        res["data_sha256"] = np.array(make_logistic(case["model"])[1])
+        res["tol"] = np.float64(logistic_smc_conditions(case, res))
+    return res
 
 
 SMC_CASES = [
@@ -386,6 +509,9 @@ SMC_CASES = [
          scale=0.35, seed=20246, init_seed=7),
     dict(name="smc_gauss3_m2048", model=dict(kind="gauss_prior_lik", D=3, data_seed=4, prior_scale=1.5), M=2048, N=3,
          scale=0.25, seed=20247, init_seed=8),
+    # the logistic-regression target (1,536 observations, D = 8) through six temperatures
+    dict(name="smc_logistic8_m256", model=dict(kind="logistic", N=1536, D=8, data_seed=53, prior_scale=2.0), M=256, N=6,
+         scale=0.1, seed=20248, init_seed=9),
 ]
 
 

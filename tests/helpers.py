@@ -25,10 +25,44 @@ SAMPLER_CASES = [
 ]
 
 
+# the logistic-regression target under the reference's own samplers (eight chains each, ids on both sides of a wavefront
+# and of a 128-chain tile) and under its tempered SMC
+LOGISTIC_SAMPLER_CASES = ["hmc_logistic16", "hmc_logistic40", "mala_logistic16", "mala_logistic40"]
+LOGISTIC_SMC_CASE = "smc_logistic8_m256"
+
+
 def load_case(name):
     z = np.load(os.path.join(GOLDEN, name + ".npz"))
     case = json.loads(str(z["case"]))
+    if case["model"]["kind"] == "logistic":  # the data is regenerated from its seed: it must be the data of the fixture
+        X, y = logistic_data(case["model"])
+        assert logistic_sha256(X, y) == str(z["data_sha256"]), "regenerated logistic data differs from the fixture's"
     return case, z
+
+
+def logistic_data(spec):
+    """(X [N, D], y [N]) of a logistic case, regenerated from default_rng(data_seed): X ~ N(0, 1 / D), theta* ~ N(0, 1),
+    y_n ~ Bernoulli(sigmoid(x_n . theta*)).  (x_n . theta* through math.fsum: no BLAS, the same bits everywhere.)"""
+    import math
+
+    g = np.random.default_rng(spec["data_seed"])
+    N, D = spec["N"], spec["D"]
+    X = g.normal(size=(N, D)) / np.sqrt(D)
+    tstar = g.normal(size=D)
+    z = np.array([math.fsum(X[n] * tstar) for n in range(N)])
+    y = (g.uniform(size=N) < 1.0 / (1.0 + np.exp(-z))).astype(np.float64)
+    return X, y
+
+
+def logistic_sha256(X, y):
+    import hashlib
+
+    return hashlib.sha256(np.ascontiguousarray(X).tobytes() + np.ascontiguousarray(y).tobytes()).hexdigest()
+
+
+def case_chain_ids(case, C):
+    """The chain index (second word of the Philox key) of every stored chain: 0 .. C - 1 unless the case lists them."""
+    return list(case.get("chain_ids", range(C)))
 
 
 def oracle_model(spec):
@@ -45,6 +79,9 @@ def oracle_model(spec):
         from tests.host_models import Binomial
 
         return Binomial(alpha=2, beta=3, x=5, N=15)
+    if kind == "logistic":
+        X, y = logistic_data(spec)
+        return omodels.LogisticRegression(X, y, prior_scale=spec["prior_scale"])
     raise KeyError(kind)
 
 
@@ -145,6 +182,8 @@ def smc_model(spec):
         g = np.random.default_rng(spec["data_seed"])
         D = spec["D"]
         return omodels.GaussPriorLik(y=g.normal(size=D) * 1.5, prec=np.logspace(0, 1.5, D), prior_scale=spec["prior_scale"])
+    if spec["kind"] == "logistic":
+        return oracle_model(spec)
     raise KeyError(spec)
 
 

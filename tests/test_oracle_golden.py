@@ -8,7 +8,8 @@ import numpy as np
 import pytest
 
 from oracle import diagnostics as od
-from tests.helpers import SAMPLER_CASES, load_case, oracle_model, oracle_sampler, rng_state_words
+from tests.helpers import (LOGISTIC_SAMPLER_CASES, SAMPLER_CASES, case_chain_ids, load_case, oracle_model, oracle_sampler,
+                           rng_state_words)
 
 
 class _Counting:
@@ -54,6 +55,33 @@ def test_sampler_matches_reference_bit_for_bit(name):
         if case["alg"] == "drghmc":
             np.testing.assert_array_equal(s._rho, z["rho_final"][c])
         del extra
+
+
+@pytest.mark.parametrize("name", LOGISTIC_SAMPLER_CASES)
+def test_logistic_sampler_matches_reference_bit_for_bit(name):
+    """The reference's HMCDiag / MALA on oracle.models.LogisticRegression (data regenerated from its seed, its SHA-256
+    checked on load): theta, logp, the accept decisions and the final stream state of the eight stored chain ids."""
+    case, z = load_case(name)
+    N, C, D = z["draws"].shape
+    ids = case_chain_ids(case, C)
+    assert ids == list(z["chain_ids"]) == [0, 1, 63, 64, 65, 127, 128, 129] and (N, C) == (30, 8)
+    assert 0.0 < float(z["tol"]) <= 1e-9
+    acc = z["accepted"]
+    assert np.all(acc.sum(axis=0) >= 3) and np.all((~acc).sum(axis=0) >= 3)
+    model = _Counting(oracle_model(case["model"]))
+    for j, c in enumerate(ids):
+        s = oracle_sampler(case, c, model=model)
+        prev = np.asarray(s._theta, dtype=np.float64).copy()
+        np.testing.assert_array_equal(prev, z["theta0"][j])
+        for n in range(N):
+            before = model.n
+            th, lp = s.sample()
+            assert np.array_equal(th, z["draws"][n, j]), (name, c, n)
+            assert lp == z["logp"][n, j], (name, c, n)
+            assert bool(np.any(th != prev)) == bool(acc[n, j]), (name, c, n)
+            assert model.n - before == (case["steps"] + 1 if case["alg"] == "hmc" else 1)
+            prev = np.array(th, dtype=np.float64)
+        np.testing.assert_array_equal(rng_state_words(s._rng), z["rng_state"][j])
 
 
 def test_hmc_one_step_equals_mala():
@@ -185,7 +213,7 @@ def _oracle_smc(case, z, stream):
 
 
 @pytest.mark.parametrize("source", ["restated_mt19937", "numpy_randomstate", "replay"])
-@pytest.mark.parametrize("name", ["smc_ref_binomial", "smc_gauss5_m512", "smc_gauss3_m2048"])
+@pytest.mark.parametrize("name", ["smc_ref_binomial", "smc_gauss5_m512", "smc_gauss3_m2048", "smc_logistic8_m256"])
 def test_smc_matches_reference_bit_for_bit(name, source):
     from oracle import smc as osmc
     from oracle.rng import LegacyStream
