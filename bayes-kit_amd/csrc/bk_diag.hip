@@ -157,7 +157,7 @@ __global__ __launch_bounds__(PC_BLOCK) void k_ess(const double* x, i64 ld, i64 N
     } else {
       if (pair < 0.0) break;
       if (estimator == 0) {
-        prev_min = prev_min < pair ? prev_min : pair;  // iat.py:132
+        prev_min = pair < prev_min ? pair : prev_min;  // iat.py:132: Python's min(prev_min, pair) -- a NaN pair leaves it
         total = total + prev_min;
       } else {
         total = total + pair;
@@ -317,7 +317,7 @@ __global__ __launch_bounds__(ET_BLOCK) void k_ess_tile(const double* x, i64 ld, 
         } else {
           if (pk < 0.0) { done = true; break; }
           if (estimator == 0) {
-            prev_min = prev_min < pk ? prev_min : pk;  // iat.py:132
+            prev_min = pk < prev_min ? pk : prev_min;  // iat.py:132 (min(prev_min, pk))
             total = total + prev_min;
           } else {
             total = total + pk;
@@ -352,7 +352,7 @@ __global__ __launch_bounds__(256) void k_iat_from_acor(const double* acor, i64 l
     } else {
       if (pk < 0.0) break;
       if (estimator == 0) {
-        prev_min = prev_min < pk ? prev_min : pk;
+        prev_min = pk < prev_min ? pk : prev_min;  // iat.py:132: min(prev_min, pk) keeps prev_min when pk is NaN
         total = total + prev_min;
       } else {
         total = total + pk;

@@ -630,7 +630,7 @@ class FakeOps:
                     if pk < 0:
                         break
                     if estimator == 0:
-                        prev_min = min(prev_min, pk)
+                        prev_min = min(prev_min, pk)  # iat.py:132: Python's min keeps prev_min when pk is NaN
                         total += prev_min
                     else:
                         total += pk
