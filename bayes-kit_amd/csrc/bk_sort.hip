@@ -6,9 +6,13 @@
 // The cross-rank choreography (samples -> splitters -> all_to_all of buckets -> ranks back) lives in
 // bayes_kit_amd/diagnostics.py on torch.distributed (RCCL over xGMI; gloo in the CPU tests).
 //
-// The sort: least-significant-digit radix sort, 8 passes of 8 bits over the order-preserving image of the keys
-// (sign bit flipped for non-negative doubles, all bits for negative ones: -0.0 < +0.0, -inf first, +inf / nan
-// last).  A pass is three launches:
+// The sort: least-significant-digit radix sort, 8 passes of 8 bits over the order-preserving image of the keys'
+// bit patterns (sign bit flipped where it is clear, all bits where it is set).  The order is therefore the raw
+// order of the bit patterns: sign-bit NaNs first (0.0 / 0.0 on an x86 host is one), -inf, ..., -0.0, +0.0, ...,
+// +inf, positive NaNs last; keys come back with their own bits.  No 64-bit image can put the NaNs of both signs
+// last and keep the bits (the two ranges of images would collide), so callers that want numpy's order canonicalise
+// first (diagnostics._canonical_keys).  bk_count_below: IEEE `<`, so a NaN query gives 0; n = 0 gives 0.
+// A pass is three launches:
 //   k_sort_hist     one workgroup per tile of 4,096 keys: the tile's digit histogram (LDS atomics), stored
 //                   digit-major [256][tiles]
 //   k_sort_scan     one workgroup per digit: exclusive scan of its row of tile counts, digit totals; the last

@@ -788,11 +788,22 @@ int bk_rank_normalize(const double* rank, double S, double* out, int64_t n, void
 
 /* Building blocks of pooled ranks (rhat.py:27-59: every draw replaced by its rank among ALL draws
  * of ALL chains) without replicating the draws on every rank -- a sample sort:
- *   bk_sort_by_key    stable ascending sort of (key, payload) pairs (keys double, -0.0 < +0.0, NaNs
- *                     last; equal keys keep their input order).  `work`: caller scratch of
- *                     bk_sort_by_key_work_bytes(n) bytes.  In and out arrays must not overlap.
- *   bk_count_below    out[i] = number of sorted_keys[0..n) strictly below queries[i]  (bucket
- *                     boundaries for the splitters)
+ *   bk_sort_by_key    stable sort of (key, payload) pairs by the RAW ORDER OF THE KEYS' BIT PATTERNS: a key
+ *                     with bits b sorts by ~b if its sign bit is set, by b | 2^63 otherwise.  For every
+ *                     non-NaN double that is ascending order with -0.0 < +0.0; a NaN sorts by its sign
+ *                     bit: sign-bit NaNs FIRST (before -inf), positive NaNs last (after +inf).  0.0 / 0.0
+ *                     on an x86 host is a sign-bit NaN: a caller that wants NumPy's order (every NaN
+ *                     last, the two zeros tied) canonicalises its keys first, as
+ *                     bayes_kit_amd.diagnostics._canonical_keys does.  Equal bit patterns keep their
+ *                     input order; every key comes back with its own bits (NaN payloads included) and
+ *                     every payload with all 64 of its own.  `work`: caller scratch of
+ *                     bk_sort_by_key_work_bytes(n) bytes, 16-byte aligned.  In and out arrays must not
+ *                     overlap; n <= 2^31 - 1 (BK_E_ARG otherwise; bk_sort_by_key_work_bytes returns -1).
+ *   bk_count_below    out[i] = number of sorted_keys[0..n) strictly below queries[i] in IEEE comparison
+ *                     (bucket boundaries for the splitters), by binary search: sorted_keys ascending,
+ *                     NaNs, if any, at the end.  A NaN query is below nothing and gives 0 (not n, as
+ *                     np.searchsorted would).  n = 0 gives 0 for every query, and sorted_keys may then
+ *                     be null.
  *   bk_scatter_ranks  out[payload[j]] = base + (j + 1), j < n: the (1-based, as doubles) ranks of a
  *                     sorted run whose first element has `base` elements before it. */
 int64_t bk_sort_by_key_work_bytes(int64_t n);

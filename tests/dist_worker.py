@@ -123,18 +123,45 @@ def main():
     from bayes_kit_amd import diagnostics as dg
 
     rs = np.random.default_rng(11)
+    neg_nan = np.copysign(np.nan, -1.0)
+
+    def with_specials(x):  # NaNs of both signs, both infinities and both zeros over a fifth of the draws
+        spots = rs.permutation(x.size)[:x.size // 5]
+        x.reshape(-1)[spots] = np.array([np.nan, neg_nan, np.inf, -np.inf, 0.0, -0.0])[rs.integers(0, 6, size=len(spots))]
+        return x
+
+    def split_range(sign):  # every draw of rank 0 (chains 0, 1) below (sign = 1) or above every draw of rank 1
+        x = rs.normal(size=(25, 4))
+        x[:, :2] -= sign * 100.0
+        x[:, 2:] += sign * 100.0
+        return x
+
     for C_tot, N_t, make in ((7, 50, lambda: rs.integers(0, 9, size=(50, 7)).astype(np.float64)),
                              (6, 40, lambda: np.sort(rs.normal(size=(40 * 6))).reshape(6, 40).T.copy()),
-                             (9, 31, lambda: rs.normal(size=(31, 9)))):
+                             (9, 31, lambda: rs.normal(size=(31, 9))),
+                             # every value equal: every splitter repeats, one bucket is empty
+                             (4, 20, lambda: np.full((20, 4), 2.5)),
+                             (5, 30, lambda: rs.integers(0, 2, size=(30, 5)).astype(np.float64)),   # two distinct values
+                             (6, 40, lambda: with_specials(rs.normal(size=(40, 6)))),
+                             (6, 200, lambda: with_specials(np.round(rs.normal(size=(200, 6)), 1))),  # ... more draws than samples
+                             (4, 10, lambda: np.where(rs.integers(0, 2, size=(10, 4)) == 0, np.nan, neg_nan)),  # every draw NaN
+                             (2, 3, lambda: rs.normal(size=(3, 2))),        # a shard smaller than its 128 samples
+                             (1, 5, lambda: rs.normal(size=(5, 1))),        # rank 1 holds an [N, 0] shard
+                             (4, 25, lambda: split_range(1.0)),
+                             (4, 25, lambda: split_range(-1.0))):
         full_np = make()
         shared = [full_np if rank == 0 else None]
         dist.broadcast_object_list(shared, src=0)
         full_np = shared[0]
         f8, n8 = bk.dist.shard(C_tot)
         mine = torch.from_numpy(np.ascontiguousarray(full_np[:, f8:f8 + n8]))
+        assert full_np.shape == (N_t, C_tot) and mine.shape == (N_t, n8)
         got = dg._ranks_pooled_across_ranks(mine, ops)
         want = dg.rank_chains(torch.from_numpy(full_np), ops=ops)[:, f8:f8 + n8]
-        assert torch.equal(got, want), (C_tot, N_t)
+        assert got.shape == want.shape and torch.equal(got, want), (C_tot, N_t)
+        # ... and rank_chains of the pooled series is NumPy's stable ranking (rhat.py:51-52), on this input too
+        flat_np = full_np.T.reshape(-1)
+        assert np.array_equal(want.numpy(), (flat_np.argsort(kind="stable").argsort() + 1).reshape(C_tot, N_t).T[:, f8:f8 + n8])
     total = bk.dist.sum_over_ranks(float(n))
     assert total == C
     dist.barrier()

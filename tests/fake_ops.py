@@ -7,6 +7,8 @@ of include/bkhip.h is specified to compute; random numbers come from numpy Gener
 rebuilt from / written back to the same per-chain state table the device uses.  Nothing in
 the product imports this file; on the GPU box the samplers run on the HIP library.
 """
+import ctypes
+
 import numpy as np
 import torch
 
@@ -18,12 +20,63 @@ def _np(t):
     return None if t is None else t.numpy()
 
 
+def _host(addr, n, ctype, dtype):
+    return np.frombuffer((ctype * n).from_address(addr), dtype=dtype) if n else np.zeros(0, dtype=dtype)
+
+
+class FakeSortLib:
+    """``ops.sort_lib``, what tests/sort_parity.py calls where the device has ``ops.lib``: bk_sort_by_key_work_bytes / bk_sort_by_key / bk_count_below on host pointers, with
+    the argument checks include/bkhip.h states.  The sort scribbles over all of `work`, like a kernel that uses every
+    byte it asked for, and no further."""
+
+    E_ARG = -1
+
+    def __init__(self, ops):
+        self._ops = ops
+
+    @staticmethod
+    def bk_sort_by_key_work_bytes(n):
+        if n <= 0:
+            return 0
+        if n > 0x7FFFFFFF:
+            return -1
+        arr = -(-n * 8 // 256) * 256                      # sort_plan of csrc/bk_sort.hip
+        return 2 * arr + -(-n // 4096) * 256 * 4 + (2 * 256 + 2) * 4
+
+    def bk_sort_by_key(self, keys_in, keys_out, vals_in, vals_out, n, work, work_bytes, stream):
+        if n < 0 or n > 0x7FFFFFFF or (n > 0 and not (keys_in and keys_out and vals_in and vals_out)):
+            return self.E_ARG
+        if n == 0:
+            return 0
+        nb = self.bk_sort_by_key_work_bytes(n)
+        if not work or work_bytes < nb or work % 16 or keys_in == keys_out or vals_in == vals_out:
+            return self.E_ARG
+        _host(work, nb, ctypes.c_uint8, np.uint8)[:] = 0x5A
+        k = torch.from_numpy(_host(keys_in, n, ctypes.c_uint64, np.uint64).view(np.float64))
+        v = torch.from_numpy(_host(vals_in, n, ctypes.c_int64, np.int64))
+        ko, vo = self._ops.sort_by_key(k, v)
+        _host(keys_out, n, ctypes.c_uint64, np.uint64)[:] = ko.numpy().view(np.uint64)
+        _host(vals_out, n, ctypes.c_int64, np.int64)[:] = vo.numpy()
+        return 0
+
+    def bk_count_below(self, sorted_keys, n, queries, m, out, stream):
+        if n < 0 or m < 0 or (m > 0 and not (queries and out)) or (n > 0 and not sorted_keys):
+            return self.E_ARG
+        if m == 0:
+            return 0
+        k = torch.from_numpy(_host(sorted_keys, n, ctypes.c_double, np.float64))
+        q = torch.from_numpy(_host(queries, m, ctypes.c_double, np.float64))
+        _host(out, m, ctypes.c_int64, np.int64)[:] = self._ops.count_below(k, q).numpy()
+        return 0
+
+
 class FakeOps:
     name = "fake-cpu"
 
     def __init__(self):
         self.device = torch.device("cpu")
         self.calls = {}
+        self.sort_lib = FakeSortLib(self)  # (not `lib`: the stand-in has no C ABI, and bodies that need one ask for that name)
 
     def _count(self, name):
         self.calls[name] = self.calls.get(name, 0) + 1
@@ -585,11 +638,25 @@ class FakeOps:
         out.numpy().reshape(-1)[...] = scipy.stats.norm.ppf((rank.numpy().reshape(-1) - 0.325) / (S - 0.25))
 
     def sort_by_key(self, keys, vals):
-        ko, order = torch.sort(keys, stable=True)
-        return ko, vals[order]
+        # bk_sort_by_key's raw contract: stable, by the order of the bit patterns (image = ~b for a set sign bit, else
+        # b | 2^63: -0.0 before +0.0, sign-bit NaNs first, positive NaNs last), every key back with its own bits --
+        # not torch.sort, which ties the zeros and puts every NaN last
+        b = keys.contiguous().numpy().view(np.uint64)
+        img = np.where((b >> np.uint64(63)).astype(bool), ~b, b | np.uint64(1 << 63))
+        order = torch.from_numpy(np.argsort(img, kind="stable"))
+        return keys[order], vals[order]
 
     def count_below(self, sorted_keys, queries):
-        return torch.searchsorted(sorted_keys.contiguous(), queries.contiguous(), right=False)
+        # k_count_below's binary search on IEEE `<`, one query per lane: a NaN query compares false throughout and gives 0
+        k, q = sorted_keys.contiguous().numpy(), queries.contiguous().numpy()
+        lo, hi = np.zeros(len(q), dtype=np.int64), np.full(len(q), len(k), dtype=np.int64)
+        while (lo < hi).any():
+            on = lo < hi
+            mid = (lo + hi) >> 1
+            with np.errstate(invalid="ignore"):
+                less = k[np.minimum(mid, len(k) - 1)] < q
+            lo, hi = np.where(on & less, mid + 1, lo), np.where(on & ~less, mid, hi)
+        return torch.from_numpy(lo)
 
     def scatter_ranks(self, payload, base, out):
         out[payload] = base + torch.arange(1, payload.numel() + 1, dtype=out.dtype)
