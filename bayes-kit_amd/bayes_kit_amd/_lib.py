@@ -61,12 +61,16 @@ SIGNATURES = {
     "bk_scatter_columns": [P, P, I, I, P, P, P, P, P, P, I, I, P, P, P, P],
     "bk_mala_propose": [c_int, P, I, P, P, P, I, F, F, I, I, P],
     "bk_mala_propose_from_normals": [P, P, P, I, I, P, I, F, F, I, I, P],
+    "bk_mala_propose_from_normals_precond": [P, P, P, I, I, P, P, I, F, F, I, I, P],
     "bk_normals_chain_major": [c_int, P, I, P, I, I, I, P, I, P],
     "bk_mala_logq": [P, P, P, P, I, F, P, P, I, I, P],
+    "bk_mala_logq_precond": [P, P, P, P, I, P, F, P, P, I, I, P],
     "bk_mala_single_draw": [c_int, P, I, P, P, P, P, P, P, P, I, P, P, F, F, I, c_int, F, P],
     "bk_mala_step_supported": [I, I, I],
     "bk_mala_step": [P, P, P, P, P, I, P, P, P, P, I, F, F, P, P, P, I, I, P],
     "bk_mala_step_gaussian": [P, P, P, I, P, P, P, P, P, I, F, F, P, P, P, I, I, P],
+    "bk_mala_step_precond": [P, P, P, P, P, I, P, P, P, P, P, I, F, F, P, P, P, I, I, P],
+    "bk_mala_step_gaussian_precond": [P, P, P, I, P, P, P, P, P, P, I, F, F, P, P, P, I, I, P],
     "bk_target_iso_gaussian_grad": [P, P, P, I, I, I, P],
     "bk_target_diag_gaussian_grad": [P, P, P, I, P, I, I, P],
     "bk_target_funnel_grad": [P, P, P, I, I, I, P],
@@ -539,6 +543,16 @@ class Ops:
         self._call("bk_mala_propose_from_normals", ptr(theta), ptr(grad), ptr(z), z.stride(0), z.stride(1),
                    ptr(theta_prop), ld, eps, sqrt2eps, C, D, self._s())
 
+    def mala_propose_from_normals_precond(self, theta, grad, z, precond, theta_prop, eps, sqrt2eps):
+        """theta_prop = (theta + eps*(v*grad)) + sqrt2eps*(sqrt(v)*z); precond: the packed [3, D] {v, sqrt(v), 1/v}; z as in
+        mala_propose_from_normals."""
+        D, C = theta.shape
+        ld = _ld(theta)
+        assert _ld(grad) == ld and _ld(theta_prop) == ld and tuple(z.shape) == (D, C)
+        assert precond.is_contiguous() and tuple(precond.shape) == (3, D)
+        self._call("bk_mala_propose_from_normals_precond", ptr(theta), ptr(grad), ptr(z), z.stride(0), z.stride(1),
+                   ptr(precond), ptr(theta_prop), ld, eps, sqrt2eps, C, D, self._s())
+
     def normals_chain_major(self, kind, state, zt, D, snapshot=None, max_workgroups=0):
         """zt[c, :D] = the next D standard normals of chain c; `snapshot` (optional, a table like
         `state`) receives the stream table as it was before the call; max_workgroups > 0: a background launch
@@ -554,6 +568,15 @@ class Ops:
         ld = _ld(theta)
         assert _ld(grad) == ld and _ld(theta_prop) == ld and _ld(grad_prop) == ld
         self._call("bk_mala_logq", ptr(theta), ptr(grad), ptr(theta_prop), ptr(grad_prop), ld, eps,
+                   ptr(lp_forward), ptr(lp_reverse), C, D, self._s())
+
+    def mala_logq_precond(self, theta, grad, theta_prop, grad_prop, precond, eps, lp_forward, lp_reverse):
+        """mala_logq under the packed preconditioner [3, D] {v, sqrt(v), 1/v}: x = .. - eps*(v*grad), sums of (x*x)*(1/v)."""
+        D, C = theta.shape
+        ld = _ld(theta)
+        assert _ld(grad) == ld and _ld(theta_prop) == ld and _ld(grad_prop) == ld
+        assert precond.is_contiguous() and tuple(precond.shape) == (3, D)
+        self._call("bk_mala_logq_precond", ptr(theta), ptr(grad), ptr(theta_prop), ptr(grad_prop), ld, ptr(precond), eps,
                    ptr(lp_forward), ptr(lp_reverse), C, D, self._s())
 
     def mala_step_supported(self, C, D, ld):
@@ -574,10 +597,26 @@ class Ops:
                    ptr(lp), ptr(lp_prop), ptr(log_u), ptr(zt_next), ldz, eps, sqrt2eps, ptr(mask), ptr(ret),
                    ptr(count), C, D, self._s())
 
+    def mala_step_precond(self, theta, theta_out, grad, theta_prop, grad_prop, precond, lp, lp_prop, log_u, zt_next, eps,
+                          sqrt2eps, mask, ret, count):
+        """mala_step under the packed preconditioner [3, D] {v, sqrt(v), 1/v} (bk_mala_step_precond)."""
+        D, C = theta.shape
+        ld = _ld(theta)
+        assert _ld(theta_out) == ld and _ld(grad) == ld and _ld(theta_prop) == ld and _ld(grad_prop) == ld
+        assert precond.is_contiguous() and tuple(precond.shape) == (3, D)
+        ldz = 0
+        if zt_next is not None:
+            assert zt_next.shape[0] == C and zt_next.stride(1) == 1 and zt_next.shape[1] >= D
+            ldz = zt_next.stride(0)
+        self._call("bk_mala_step_precond", ptr(theta), ptr(theta_out), ptr(grad), ptr(theta_prop), ptr(grad_prop), ld,
+                   ptr(precond), ptr(lp), ptr(lp_prop), ptr(log_u), ptr(zt_next), ldz, eps, sqrt2eps, ptr(mask), ptr(ret),
+                   ptr(count), C, D, self._s())
+
     def mala_step_gaussian(self, lam, theta, theta_out, theta_prop, lp, lp_prop, log_u, zt_next, eps, sqrt2eps, mask, ret,
-                           count):
+                           count, precond=None):
         """mala_step for the separable built-in Gaussians (lam None = identity): both gradients recomputed from theta /
-        theta_prop inside the kernel, none stored (bk_mala_step_gaussian)."""
+        theta_prop inside the kernel, none stored (bk_mala_step_gaussian); precond: the packed [3, D] {v, sqrt(v), 1/v}
+        (bk_mala_step_gaussian_precond)."""
         D, C = theta.shape
         ld = _ld(theta)
         assert _ld(theta_out) == ld and _ld(theta_prop) == ld
@@ -585,6 +624,12 @@ class Ops:
         if zt_next is not None:
             assert zt_next.shape[0] == C and zt_next.stride(1) == 1 and zt_next.shape[1] >= D
             ldz = zt_next.stride(0)
+        if precond is not None:
+            assert precond.is_contiguous() and tuple(precond.shape) == (3, D)
+            self._call("bk_mala_step_gaussian_precond", ptr(theta), ptr(theta_out), ptr(theta_prop), ld, ptr(lam),
+                       ptr(precond), ptr(lp), ptr(lp_prop), ptr(log_u), ptr(zt_next), ldz, eps, sqrt2eps, ptr(mask),
+                       ptr(ret), ptr(count), C, D, self._s())
+            return
         self._call("bk_mala_step_gaussian", ptr(theta), ptr(theta_out), ptr(theta_prop), ld, ptr(lam), ptr(lp), ptr(lp_prop),
                    ptr(log_u), ptr(zt_next), ldz, eps, sqrt2eps, ptr(mask), ptr(ret), ptr(count), C, D, self._s())
 

@@ -22,6 +22,9 @@ Two ways through the device:
 
 Both consume each chain's stream in the reference's order (D normals, then one uniform) and give
 the same draws bit for bit.
+
+``precond_diag=v`` (extension) is plain MALA on theta / sqrt(v): theta' = (theta + eps*(v*grad)) + sqrt(2 eps)*(sqrt(v)*z),
+proposal densities with x = .. - eps*(v*grad) and the sum of (x*x)*(1/v).  ``warmup`` estimates v and tunes eps from all chains.
 """
 from __future__ import annotations
 
@@ -46,17 +49,27 @@ class MALA(ManyChainSampler):
     TUNING = ("graph", "prefetch_rng", "tune_placement", "two_pass", "single_launch")
 
     def __init__(self, model, epsilon: float, init=None, seed=None, *, chains: Optional[int] = None,
-                 chain_id0: int = 0, path: str = "auto", tuning: Optional[dict] = None, ops=None, **knobs):
+                 chain_id0: int = 0, path: str = "auto", precond_diag=None, tuning: Optional[dict] = None, ops=None,
+                 **knobs):
         """The reference's arguments (mala.py:15-21), then the engine's (ManyChainSampler: chains, chain_id0, path, tuning,
         ops; path "step" and "opaque" both keep the model-opaque pair {gradient op, step kernel}).  Tuning knobs (none
         changes a result): ``graph``, ``prefetch_rng``, ``tune_placement``, ``two_pass`` (gradient op + ONE step kernel
-        per draw; default where the shape allows), ``single_launch`` (one chain: one launch per draw)."""
+        per draw; default where the shape allows), ``single_launch`` (one chain: one launch per draw).
+
+        ``precond_diag`` (extension; needs a batched device model): a length-D vector v of variances, ideally the posterior
+        variances -- the sampler is then plain MALA on theta / sqrt(v), at the cost of three more multiplies per element.
+        Every path supports it and gives the same draws bit for bit: two-pass shapes use the preconditioned step kernel
+        (bk_mala_step_precond), the built-in Gaussians their inlined one; an elementwise from_source / traced density, whose
+        compiled step kernel has no preconditioned form, falls back to the model-opaque pair of launches while a
+        preconditioner is set.  ``set_precond_diag`` replaces it between draws, ``warmup`` estimates it."""
         fuse_builtin, _ = self._resolve_path(path)
         tn = self._resolve_tuning(tuning, knobs)
         graph, prefetch_rng, tune_placement = tn.get("graph"), tn.get("prefetch_rng"), tn.get("tune_placement")
         two_pass, single_launch = tn.get("two_pass"), tn.get("single_launch")
         self._epsilon = epsilon
+        self._pd = None        # packed preconditioner [3, D] = {v, sqrt(v), 1/v} on the device (precond_diag)
         self._setup(model, None, init, seed, chains, chain_id0, ops)
+        pv = None if precond_diag is None else self._check_precond(precond_diag)
         self._init_graph(graph, prefetch_rng)
         D, C, dev = self._dim, self._C, self._ops.device
         f64 = dict(dtype=torch.float64, device=dev)
@@ -91,13 +104,16 @@ class MALA(ManyChainSampler):
             raise ValueError("two_pass=True needs a batched model, Philox streams, 32 <= D <= 1024 and an even number "
                              "of chains")
         self._two_pass = can_two_pass if two_pass is None else bool(two_pass)
-        self.path = "two-pass (bk_mala_step)" if self._two_pass else "step-by-step"
         # a separable density the library can inline: the step kernel recomputes the gradients (none is stored between draws;
-        # _grad is brought up to date when somebody asks for it)
-        self._sep_step = bool(fuse_builtin) and self._two_pass and hasattr(model, "bk_mala_step") and hasattr(model, "bk_eval")
+        # _grad is brought up to date when somebody asks for it) -- with a preconditioner only where the model's hook has
+        # the preconditioned form (the built-in Gaussians)
+        self._sep_capable = (bool(fuse_builtin) and self._two_pass and hasattr(model, "bk_mala_step")
+                             and hasattr(model, "bk_eval"))
+        self._sep_step = False
         self._grad_stale = False
-        if self._sep_step:
-            self.path = "two-pass, gradients recomputed in the step kernel (model.bk_mala_step)"
+        if pv is not None:
+            self._pack_precond(pv)
+        self._route()
         nbuf = 2 if self._prefetch else 1
         if self._chain_major:
             dp = (D + 7) // 8 * 8
@@ -143,6 +159,80 @@ class MALA(ManyChainSampler):
             self._tune_placement()
         # mala.py:31-32: (logp, grad) at theta0
         self._materialize(self._eval_grad(self._theta_dc, self._grad, self._lp), self._grad)
+
+    # -- the diagonal preconditioner ------------------------------------------------------------------------------
+    def _check_precond(self, v):
+        if not self._batched:
+            raise ValueError("precond_diag needs a batched device model (the one-launch single-chain mode is not "
+                             "preconditioned)")
+        vt = torch.as_tensor(v, dtype=torch.float64).reshape(-1)
+        if vt.shape[0] != self._dim:
+            raise ValueError(f"precond_diag has {vt.shape[0]} entries, model has {self._dim} dims")
+        vt = vt.to(self._ops.device).contiguous()
+        if not bool((torch.isfinite(vt) & (vt > 0.0)).all()):
+            raise ValueError("precond_diag must hold finite, positive variances")
+        return vt
+
+    def _pack_precond(self, vt):
+        """{v, sqrt(v), 1/v} on the device, in place once the buffer exists."""
+        if self._pd is None:
+            self._pd = torch.empty((3, self._dim), dtype=torch.float64, device=self._ops.device)
+        self._ops.precond_pack(vt, self._pd)  # (the library's own sqrt and 1/x: the same doubles on every device)
+
+    def _route(self):
+        """Which step kernel a two-pass draw uses, and `path`."""
+        sep = self._sep_capable and (self._pd is None or getattr(self._model, "bk_mala_step_precond", False) is True)
+        if self._sep_step and not sep:
+            self._fresh_grad()  # the model-opaque step kernel selects between stored gradients
+        self._sep_step = sep
+        pc = self._pd is not None
+        if getattr(self, "_single", False):
+            return
+        if sep:
+            self.path = "two-pass, gradients recomputed in the step kernel (model.bk_mala_step)"
+        elif self._two_pass and pc and self._sep_capable:
+            self.path = ("two-pass (bk_mala_step_precond): the model's inlined step kernel has no preconditioned form, "
+                         "model-opaque pair of launches")
+        elif self._two_pass:
+            self.path = "two-pass (bk_mala_step_precond)" if pc else "two-pass (bk_mala_step)"
+        else:
+            self.path = "step-by-step"
+
+    def set_precond_diag(self, v):
+        """Set or replace the diagonal preconditioner between draws (see ``precond_diag``).  Changes no logical stream
+        position: a proposal made ahead with the old v is discarded and its normals are drawn again, same values (as
+        ``refresh_cache``); captured graphs are dropped."""
+        vt = self._check_precond(v)
+        self._invalidate_pipe(restore_stream=True)
+        self._pack_precond(vt)
+        self._route()
+
+    @property
+    def precond_diag(self):
+        """The preconditioner's variances as a host array (None when not set)."""
+        return None if self._pd is None else self._pd[0].cpu().numpy().copy()
+
+    def _propose(self, th, g, z, thp, eps):
+        """theta' from drawn normals z (either layout) [mala.py:41-45]."""
+        if self._pd is None:
+            self._ops.mala_propose_from_normals(th, g, z, thp, eps, math.sqrt(2 * eps))
+        else:
+            self._ops.mala_propose_from_normals_precond(th, g, z, self._pd, thp, eps, math.sqrt(2 * eps))
+
+    def _logq(self, th, g, thp, gp, eps):
+        """Forward / reverse proposal densities [mala.py:50-53, 68-79]."""
+        if self._pd is None:
+            self._ops.mala_logq(th, g, thp, gp, eps, self._fwd, self._rev)
+        else:
+            self._ops.mala_logq_precond(th, g, thp, gp, self._pd, eps, self._fwd, self._rev)
+
+    def _state_layout_normals(self):
+        """D normals per chain in the state layout from the chain's stream (PCG64 streams or D < 32: one lane per chain,
+        the values bk_mala_propose draws inside its kernel)."""
+        if getattr(self, "_z_state", None) is None:
+            self._z_state = self._new_state()
+        self._ops.momentum_refresh(self._rng_kind, self._rng_state, None, 0.0, 1.0, self._z_state, None, None)
+        return self._z_state
 
     def _fresh_grad(self):
         """The cached gradient of the current point; the separable step kernel does not keep it (recomputed on demand)."""
@@ -217,6 +307,21 @@ class MALA(ManyChainSampler):
             # draws handed out earlier alias past state arrays: restore into a fresh one
             self._theta_dc = self._new_state()
         super().load_state_dict(sd)
+
+    def _state_extra(self):
+        return {"epsilon": float(self._epsilon), "precond_diag": None if self._pd is None else self._pd[0].cpu().clone()}
+
+    def _load_extra(self, extra):
+        # (checkpoints written before the step size and the preconditioner were carried hold neither: nothing changes)
+        if "epsilon" in extra:
+            self._epsilon = extra["epsilon"]
+        pv = extra.get("precond_diag")
+        if pv is not None:
+            self._pack_precond(self._check_precond(pv))
+            self._grad_stale = False  # (the gradient of the restored point came with it)
+            self._route()
+        elif self._pd is not None and "precond_diag" in extra:
+            raise ValueError("checkpoint was written without precond_diag, this sampler has one")
 
     def _after_load(self):
         self._grad_stale = False  # (the gradient of the restored point came with it)
@@ -362,6 +467,9 @@ class MALA(ManyChainSampler):
     def sample(self):
         if self._single:
             return self._sample_single()
+        if self._two_pass and self._pipe_valid and self._pipe_eps != float(self._epsilon):
+            # epsilon was assigned between draws (mala.py:23 is a plain attribute): the proposal made ahead used the old one
+            self._invalidate_pipe(restore_stream=True)
         self._run_draw(self._draw2 if self._two_pass else self._draw)
         if self._sep_step:
             self._grad_stale = True  # (here, not in _draw2: a replayed hipGraph does not run the Python of the draw)
@@ -380,8 +488,8 @@ class MALA(ManyChainSampler):
             # this draw's proposal from the stream's next D normals (mala.py:41-45); later draws'
             # proposals are written by the previous draw's kernel
             ops.normals_chain_major(self._rng_kind, self._rng_state, self._zt_bufs[0], self._dim)
-            ops.mala_propose_from_normals(th, self._fresh_grad(), self._z_bufs[0], thp, eps, s2)
-            self._pipe_valid, self._unit_ready = True, False
+            self._propose(th, self._fresh_grad(), self._z_bufs[0], thp, eps)
+            self._pipe_valid, self._unit_ready, self._pipe_eps = True, False, eps
         logu, zt_next = self._take_unit()
         if self._sep_step:
             self._eval_logp(thp, self._lp_p)                                                   # mala.py:46-48, log density
@@ -399,9 +507,15 @@ class MALA(ManyChainSampler):
             self._ev_ready[self._pf_slot].record(torch.cuda.current_stream())
             if not self.step_first:
                 self._start_unit(self._pf_slot, recorded=True)
-        if self._sep_step:
+        if self._sep_step and self._pd is not None:
+            self._model.bk_mala_step(th, out, thp, self._lp, self._lp_p, logu, zt_next, eps, s2,
+                                     self._mask, self._ret, self._accepted, precond=self._pd)
+        elif self._sep_step:
             self._model.bk_mala_step(th, out, thp, self._lp, self._lp_p, logu, zt_next, eps, s2,
                                      self._mask, self._ret, self._accepted)                    # mala.py:50-66
+        elif self._pd is not None:
+            ops.mala_step_precond(th, out, self._grad, thp, gp, self._pd, self._lp, self._lp_p, logu, zt_next, eps, s2,
+                                  self._mask, self._ret, self._accepted)
         else:
             ops.mala_step(th, out, self._grad, thp, gp, self._lp, self._lp_p, logu, zt_next, eps, s2,
                           self._mask, self._ret, self._accepted)                               # mala.py:50-66
@@ -415,18 +529,132 @@ class MALA(ManyChainSampler):
         th, thp = self._theta_dc, self._theta_p
         if self._prefetch:
             z, logu = self._take_randomness()
-            ops.mala_propose_from_normals(th, self._grad, z, thp, eps, math.sqrt(2 * eps))
+            self._propose(th, self._grad, z, thp, eps)
         elif self._chain_major:
             logu = self._logu
             ops.normals_chain_major(self._rng_kind, self._rng_state, self._zt_bufs[0], self._dim)
             ops.log_uniform(self._rng_kind, self._rng_state, logu)  # right after the normals: same stream order
-            ops.mala_propose_from_normals(th, self._grad, self._z_bufs[0], thp, eps, math.sqrt(2 * eps))
+            self._propose(th, self._grad, self._z_bufs[0], thp, eps)
+        elif self._pd is not None:
+            # (bk_mala_propose draws its normals inside the kernel and has no preconditioned form: the same normals from
+            # the generator, then the uniform -- the same stream order)
+            logu = self._logu
+            z = self._state_layout_normals()
+            ops.log_uniform(self._rng_kind, self._rng_state, logu)
+            self._propose(th, self._grad, z, thp, eps)
         else:
             logu = self._logu
             ops.mala_propose(self._rng_kind, self._rng_state, th, self._grad, thp, eps, math.sqrt(2 * eps))
             ops.log_uniform(self._rng_kind, self._rng_state, logu)  # right after the normals: same stream order
         gp = self._materialize(self._eval_grad(thp, self._grad_p, self._lp_p), self._grad_p)
-        ops.mala_logq(th, self._grad, thp, gp, eps, self._fwd, self._rev)
+        self._logq(th, self._grad, thp, gp, eps)
         ops.mh_accept(_lib.ACCEPT_MALA, self._lp, self._fwd, self._lp_p, self._rev, logu,
                       self._mask, self._ret, self._accepted)
         self._select(self._mask, th, thp, self._grad, gp)
+
+    # -- warmup -------------------------------------------------------------------------------------
+    def _warmup_draw(self, stat, work, zero, ratio):
+        """One draw as the step-by-step composition, whatever the sampler's own path: generator, proposal from the drawn
+        normals, the model's gradient op, proposal densities, the acceptance statistic, accept, select."""
+        ops = self._ops
+        eps = float(self._epsilon)
+        th, thp, logu = self._theta_dc, self._theta_p, self._logu
+        if self._chain_major:
+            ops.normals_chain_major(self._rng_kind, self._rng_state, self._zt_bufs[0], self._dim)
+            z = self._z_bufs[0]
+        else:
+            z = self._state_layout_normals()
+        ops.log_uniform(self._rng_kind, self._rng_state, logu)  # right after the normals: same stream order
+        self._propose(th, self._grad, z, thp, eps)
+        gp = self._materialize(self._eval_grad(thp, self._grad_p, self._lp_p), self._grad_p)
+        self._logq(th, self._grad, thp, gp, eps)
+        # the log acceptance ratio in bk_mh_accept's association, before the test overwrites lp; bk_accept_stat then takes
+        # (ratio - 0) - (0 - 0), which is exact
+        torch.sub(self._lp_p, self._lp, out=ratio)
+        torch.sub(self._rev, self._fwd, out=self._ret)
+        ratio.add_(self._ret)
+        ops.accept_stat(zero, None, ratio, None, stat, work)
+        ops.mh_accept(_lib.ACCEPT_MALA, self._lp, self._fwd, self._lp_p, self._rev, logu,
+                      self._mask, self._ret, self._accepted)
+        self._select(self._mask, th, thp, self._grad, gp)
+
+    def warmup(self, draws, target_accept=0.574, adapt_metric=True, group=None):
+        """Run `draws` draws that tune epsilon and (adapt_metric) the diagonal preconditioner from ALL chains of all ranks,
+        then keep the tuned values: afterwards the sampler samples with them.  -> the report dict of ``HMCDiag.warmup``:
+        ``stepsize`` (the tuned epsilon), ``precond_diag`` (host copy, None if none is set), per-draw ``eps`` and ``alpha``
+        histories, ``window_ends``, ``nan_chains``.
+
+        The schedule, the shrinkage of the pooled window variance, the restart rule and the sum over ranks are
+        ``HMCDiag.warmup``'s; the default target 0.574 is the asymptotically optimal acceptance of MALA (Roberts & Rosenthal
+        1998).  The statistic of a draw is mean_c min(1, exp(min(0, r_c))) of the log acceptance ratio
+        r = (lp' - lp) + (rev - fwd) (bk_accept_stat; a NaN ratio counts 0).
+
+        Warmup draws run step by step on every configuration, with nothing generated or proposed ahead: the two-pass kernel
+        writes draw n+1's proposal with draw n's epsilon, which dual averaging changes after every draw, and one kernel
+        sequence makes the report identical bit for bit whatever ``two_pass``, ``path``, ``prefetch_rng`` and ``graph`` say.
+        A proposal made ahead before the call is discarded (its normals are drawn again); afterwards graphs are dropped
+        and the next ``sample()`` makes its proposal with the final epsilon and v."""
+        from .adapt import DualAveraging, warmup_windows
+        from .diagnostics import RunningMoments, _gather_sum, pooled_variance_from_moments
+
+        draws = int(draws)
+        if draws < 1:
+            raise ValueError(f"warmup: draws must be >= 1, got {draws}")
+        if not 0.0 < float(target_accept) < 1.0:
+            raise ValueError(f"warmup: target_accept must be inside (0, 1), got {target_accept}")
+        if not self._batched:
+            raise ValueError("warmup needs a batched device model (the statistics are taken across chains)")
+        ops, dev, C, D = self._ops, self._ops.device, self._C, self._dim
+        init, term, ends = warmup_windows(draws)
+        if not adapt_metric:
+            ends = []
+        # pipeline off: back to the logical stream position, nothing made ahead
+        self._invalidate_pipe(restore_stream=True)
+        if self._prefetch and self._pf_ready:  # (step by step: the next draw's randomness was generated ahead)
+            if self._pf_event is not None:
+                torch.cuda.current_stream().wait_event(self._pf_event)
+            self._rng_state.copy_(self._rng_logical)
+        self._pf_ready, self._pf_event = False, None
+        self._fresh_grad()
+        if self._two_pass and not self._use_graph:
+            # (the state array is the last draw handed out: the in-place select below must not write into it)
+            keep = self._theta_dc
+            self._theta_dc = self._new_state()
+            self._theta_dc.copy_(keep)
+        da = DualAveraging(float(self._epsilon), float(target_accept))
+        mom = RunningMoments(D, C, ops) if ends else None
+        f64 = dict(dtype=torch.float64, device=dev)
+        stat = torch.zeros(3, **f64)  # {sum of the statistic, NaN chains, chains}
+        stat[2] = float(C)
+        work = torch.empty(max(2, 2 * ((C + 255) // 256)), **f64)
+        zero, ratio = torch.zeros(C, **f64), torch.empty(C, **f64)
+        eps_hist, alpha_hist, nan_chains = [], [], 0
+        try:
+            for it in range(draws):
+                eps_hist.append(float(self._epsilon))
+                self._warmup_draw(stat, work, zero, ratio)
+                self._draws += 1
+                tot = _gather_sum(stat, group).cpu()  # the warmup draw's one host read
+                chains_total = float(tot[2])
+                alpha = float(tot[0]) / chains_total
+                alpha_hist.append(alpha)
+                nan_chains += int(tot[1])
+                if mom is not None and init <= it < draws - term:
+                    mom.update(self._theta_dc, layout="dc")
+                eps = da.step(alpha)
+                if it + 1 in ends:
+                    n_eff = float(mom.n) * chains_total
+                    var = pooled_variance_from_moments(mom.mean, mom.m2, mom.n, ops, group)
+                    self.set_precond_diag(n_eff / (n_eff + 5.0) * var + 1e-3 * 5.0 / (n_eff + 5.0))
+                    mom.reset()
+                    eps = da.final()
+                    da.restart(eps)
+                if it + 1 == draws:
+                    eps = da.final()
+                self._epsilon = eps
+        finally:
+            del mom
+            self._grad_stale = False  # (the select above kept the stored gradient current)
+            self._invalidate_pipe(restore_stream=False)
+        return {"stepsize": float(self._epsilon), "precond_diag": self.precond_diag, "eps": eps_hist, "alpha": alpha_hist,
+                "window_ends": list(ends), "nan_chains": nan_chains}

@@ -95,11 +95,18 @@ class _GaussianLanes:
         """One leapfrog step {gradient, kick, drift} as ONE launch, theta / rho advanced in place (any D)."""
         self._get_ops().leapfrog_step_gaussian(self._lam_or_none(theta.device), theta, rho, metric, h, n_dev=n_dev)
 
-    def bk_mala_step(self, theta, theta_out, theta_prop, lp, lp_prop, log_u, zt_next, eps, sqrt2eps, mask, ret, count):
+    bk_mala_step_precond = True  # (bk_mala_step takes precond=: the packed diagonal preconditioner of MALA(precond_diag=))
+
+    def bk_mala_step(self, theta, theta_out, theta_prop, lp, lp_prop, log_u, zt_next, eps, sqrt2eps, mask, ret, count,
+                     precond=None):
         """MALA's step kernel (proposal densities, accept, select, next proposal; mala.py:41-66) with the density's term inlined:
         both gradients recomputed from theta / theta_prop, none stored (56 D bytes per chain-draw instead of 88 D)."""
-        self._get_ops().mala_step_gaussian(self._lam_or_none(theta.device), theta, theta_out, theta_prop, lp, lp_prop, log_u,
-                                           zt_next, eps, sqrt2eps, mask, ret, count)
+        ops, lam = self._get_ops(), self._lam_or_none(theta.device)
+        if precond is None:  # (positional: an ops object from before the preconditioner keeps working)
+            ops.mala_step_gaussian(lam, theta, theta_out, theta_prop, lp, lp_prop, log_u, zt_next, eps, sqrt2eps, mask, ret, count)
+        else:
+            ops.mala_step_gaussian(lam, theta, theta_out, theta_prop, lp, lp_prop, log_u, zt_next, eps, sqrt2eps, mask, ret, count,
+                                   precond=precond)
 
 
 class IsoGaussian(_GaussianLanes, _BuiltinTarget):

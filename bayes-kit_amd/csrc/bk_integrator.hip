@@ -518,10 +518,12 @@ __global__ __launch_bounds__(256) void k_blend_v2(const uint8_t* mask, const dou
 }
 
 // ---- MALA proposal log densities --------------------------------------------------------
+// PC (bk_mala_logq_precond): x = .. - eps*(v*grad), the sums take (x*x)*(1/v); pc = the packed {v, sqrt(v), 1/v}
+template <bool PC>
 __global__ __launch_bounds__(RED_BLOCK) void k_mala_logq(const double* th, const double* g,
                                                          const double* thp, const double* gp, i64 ld,
                                                          double eps, double* fwd, double* rev, i64 C,
-                                                         i64 D) {
+                                                         i64 D, const double* __restrict__ pc) {
   __shared__ double part_f[RED_WAVES][BK_WAVE];
   __shared__ double part_r[RED_WAVES][BK_WAVE];
   const int lane = threadIdx.x & (BK_WAVE - 1), w = bk_wave_id();
@@ -545,10 +547,18 @@ __global__ __launch_bounds__(RED_BLOCK) void k_mala_logq(const double* th, const
 #pragma unroll
       for (int u = 0; u < U; ++u)
         if (d0 + u < dhi) {
-          double xf = (p[u] - a[u]) - eps * b[u];  // mala.py:78
-          double xr = (a[u] - p[u]) - eps * q[u];
-          sf = sf + xf * xf;
-          sr = sr + xr * xr;
+          if (PC) {
+            const double v = pc[d0 + u], iv = pc[2 * D + d0 + u];
+            double xf = (p[u] - a[u]) - eps * (v * b[u]);
+            double xr = (a[u] - p[u]) - eps * (v * q[u]);
+            sf = sf + (xf * xf) * iv;
+            sr = sr + (xr * xr) * iv;
+          } else {
+            double xf = (p[u] - a[u]) - eps * b[u];  // mala.py:78
+            double xr = (a[u] - p[u]) - eps * q[u];
+            sf = sf + xf * xf;
+            sr = sr + xr * xr;
+          }
         }
     }
   }
@@ -799,8 +809,20 @@ int bk_mala_logq(const double* theta, const double* grad, const double* theta_pr
     return BK_E_ARG;
   if (ld < C) return BK_E_ALIGN;
   if (C == 0) return BK_OK;
-  k_mala_logq<<<dim3((unsigned)bk_cdiv(C, BK_WAVE)), dim3(RED_BLOCK), 0, bk_stream(stream)>>>(
-      theta, grad, theta_prop, grad_prop, ld, eps, lp_forward, lp_reverse, C, D);
+  k_mala_logq<false><<<dim3((unsigned)bk_cdiv(C, BK_WAVE)), dim3(RED_BLOCK), 0, bk_stream(stream)>>>(
+      theta, grad, theta_prop, grad_prop, ld, eps, lp_forward, lp_reverse, C, D, nullptr);
+  BK_RETURN_LAUNCH_STATUS();
+}
+
+int bk_mala_logq_precond(const double* theta, const double* grad, const double* theta_prop,
+                         const double* grad_prop, int64_t ld, const double* precond, double eps,
+                         double* lp_forward, double* lp_reverse, int64_t C, int64_t D, void* stream) {
+  if (!theta || !grad || !theta_prop || !grad_prop || !precond || !lp_forward || !lp_reverse || C < 0 || D < 0)
+    return BK_E_ARG;
+  if (ld < C) return BK_E_ALIGN;
+  if (C == 0 || D == 0) return BK_OK;
+  k_mala_logq<true><<<dim3((unsigned)bk_cdiv(C, BK_WAVE)), dim3(RED_BLOCK), 0, bk_stream(stream)>>>(
+      theta, grad, theta_prop, grad_prop, ld, eps, lp_forward, lp_reverse, C, D, precond);
   BK_RETURN_LAUNCH_STATUS();
 }
 

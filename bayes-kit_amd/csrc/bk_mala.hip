@@ -26,6 +26,20 @@
 //
 // Memory shape: a workgroup's rows are 16 chains = 128 B wide (one L2 line per row and array);
 // a wavefront instruction covers 8 rows x 128 B.
+//
+// Diagonal preconditioner (template flag PC, bk_mala_step_precond): the packed precond[3][D] = {v, sqrt(v), 1/v} of
+// bk_precond_pack enters as  eps*(v*grad)  in both densities and the next proposal,  (x*x)*(1/v)  in the sums and
+// s*(sqrt(v)*z)  on the noise -- plain MALA on theta/sqrt(v).  The three vectors depend on the row only and come from LDS:
+// * registers: a thread's E rows would need 4 E more of them in phase 1 (v and 1/v), and 192 of its 256 hold data;
+// * per-slot buffer loads: in phase 4 they would sit between the stores, and any wait on them is a vmcnt wait that
+//   the stores count in (below);
+// * LDS: 2 rows x 64 E doubles (16 KiB at E = 16 of the ~27 free beside the 128 KiB of grad' / the normals; the normals'
+//   generator still fits beside a step workgroup with its 6).  v and 1/v are staged by LDS-DMA (4 B per lane: row 1 and
+//   2 of the pack start at D*8 bytes, not 16-byte aligned for odd D) together with the block's loads and are covered by
+//   the vmcnt(0) that phase 1 has anyway; sqrt(v) replaces 1/v, dead after the sums, together with the normals' DMA, under
+//   phase 4's own vmcnt(0).  Reads are ds_read_b64 broadcasts (the 8 pairs of a row share an address): lgkmcnt only.
+// Cost: 3 E/4 more VMEM instructions per wavefront (a row is 2 E chunks of 256 B, dealt to 8 wavefronts; three rows), one
+// more barrier in phase 1, and three multiplies per element.  With PC = false none of this is instantiated.
 #include "bk_common.hpp"
 
 namespace {
@@ -45,6 +59,7 @@ struct MsLds {
   static constexpr int Z_BYTES = MS_CHAINS * ZPITCH * 8;
   static constexpr int BIG_BYTES = Q_BYTES > Z_BYTES ? Q_BYTES : Z_BYTES;
   static constexpr int RED_DOUBLES = MS_WAVES * MS_PAIRS * 4;
+  static constexpr int PC_DOUBLES = MS_ROWS * E;  // one row of the preconditioner, padded to the slots
 };
 
 template <bool NT>
@@ -77,14 +92,30 @@ constexpr unsigned BK_RSRC_FLAGS = 0x00020000u;  // raw buffer, 32-bit data form
 __device__ __forceinline__ dvec2 as_d2(u32x4 v) { return __builtin_bit_cast(dvec2, v); }
 __device__ __forceinline__ u32x4 as_u4(dvec2 v) { return __builtin_bit_cast(u32x4, v); }
 
-template <int E, bool NT>
+// One row of the packed preconditioner (D doubles at `row`, 8-byte aligned) into LDS by LDS-DMA, 256 B per wavefront
+// instruction, the chunks dealt round robin to the 8 wavefronts; cells of rows >= D receive 0 (range check).
+template <int E>
+__device__ __forceinline__ void ms_stage_precond_row(const double* row, i64 D, double* dst, int w, int lane) {
+  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void*)row, 0, (unsigned)(D * 8), BK_RSRC_FLAGS);
+#pragma unroll
+  for (int k = 0; k < (2 * E + MS_WAVES - 1) / MS_WAVES; ++k) {
+    const int q = w + MS_WAVES * k;  // chunk of 32 doubles
+    if (q < 2 * E)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)(dst + 32 * q), 4,
+                                               4u * lane, 256 * q, 0, 0);
+  }
+}
+
+template <int E, bool NT, bool PC>
 __global__ __launch_bounds__(MS_THREADS) void k_mala_step(
     const double* th, double* out, double* g, double* thp, const double* gp, i64 ld, double* lp,
     const double* __restrict__ lp_p, const double* __restrict__ log_u, const double* zt, i64 ldz, double eps,
-    double s, uint8_t* mask, double* ret, uint32_t* count, i64 C, i64 D) {
+    double s, uint8_t* mask, double* ret, uint32_t* count, i64 C, i64 D, const double* pc) {
   using L = MsLds<E>;
   __shared__ __attribute__((aligned(16))) unsigned char big[L::BIG_BYTES];
   __shared__ double red[L::RED_DOUBLES];
+  __shared__ double pcv[PC ? L::PC_DOUBLES : 1];  // v
+  __shared__ double pcx[PC ? L::PC_DOUBLES : 1];  // 1/v in phase 1, sqrt(v) in phase 4
   dvec2* qs = reinterpret_cast<dvec2*>(big);
   double* zs = reinterpret_cast<double*>(big);
   constexpr int AUX = NT ? 2 : 0;
@@ -116,6 +147,10 @@ __global__ __launch_bounds__(MS_THREADS) void k_mala_step(
   // e*512 + t is written by lane t's own load), so it costs no staging registers while the other
   // three arrays fill 192 VGPRs; all 4 E loads of a thread are in flight together.
   dvec2 a[E], b[E], p[E];
+  if (PC) {
+    ms_stage_precond_row<E>(pc, D, pcv, w, lane);
+    ms_stage_precond_row<E>(pc + 2 * D, D, pcx, w, lane);
+  }
 #pragma unroll
   for (int e = 0; e < E; ++e)
     __builtin_amdgcn_raw_ptr_buffer_load_lds(r_gp, (__attribute__((address_space(3))) void*)(big + (e * MS_THREADS + w * BK_WAVE) * 16),
@@ -128,18 +163,30 @@ __global__ __launch_bounds__(MS_THREADS) void k_mala_step(
   }
   __builtin_amdgcn_sched_barrier(0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wavefront's grad' slots have landed in LDS
+  if (PC) __syncthreads();  // ... and every wavefront's chunks of v and 1/v
   double sf0 = 0.0, sf1 = 0.0, sr0 = 0.0, sr1 = 0.0;
 #pragma unroll
   for (int e = 0; e < E; ++e) {
     const dvec2 q = qs[e * MS_THREADS + t];
     // x = (theta' - theta) - eps*grad ; reverse: (theta - theta') - eps*grad'   (mala.py:78)
     // (rows >= D were loaded as zeros: x = 0 and the sums receive +0.0)
-    const double xf0 = (p[e].x - a[e].x) - eps * b[e].x, xf1 = (p[e].y - a[e].y) - eps * b[e].y;
-    const double xr0 = (a[e].x - p[e].x) - eps * q.x, xr1 = (a[e].y - p[e].y) - eps * q.y;
-    sf0 = sf0 + xf0 * xf0;
-    sf1 = sf1 + xf1 * xf1;
-    sr0 = sr0 + xr0 * xr0;
-    sr1 = sr1 + xr1 * xr1;
+    if (PC) {
+      // x = (theta' - theta) - eps*(v*grad), weighted (x*x)*(1/v); rows >= D: v = 1/v = 0 as well, the sums receive +0.0
+      const double v = pcv[r + MS_ROWS * e], iv = pcx[r + MS_ROWS * e];
+      const double xf0 = (p[e].x - a[e].x) - eps * (v * b[e].x), xf1 = (p[e].y - a[e].y) - eps * (v * b[e].y);
+      const double xr0 = (a[e].x - p[e].x) - eps * (v * q.x), xr1 = (a[e].y - p[e].y) - eps * (v * q.y);
+      sf0 = sf0 + (xf0 * xf0) * iv;
+      sf1 = sf1 + (xf1 * xf1) * iv;
+      sr0 = sr0 + (xr0 * xr0) * iv;
+      sr1 = sr1 + (xr1 * xr1) * iv;
+    } else {
+      const double xf0 = (p[e].x - a[e].x) - eps * b[e].x, xf1 = (p[e].y - a[e].y) - eps * b[e].y;
+      const double xr0 = (a[e].x - p[e].x) - eps * q.x, xr1 = (a[e].y - p[e].y) - eps * q.y;
+      sf0 = sf0 + xf0 * xf0;
+      sf1 = sf1 + xf1 * xf1;
+      sr0 = sr0 + xr0 * xr0;
+      sr1 = sr1 + xr1 * xr1;
+    }
     // at most 4 LDS reads ahead: hoisting all E of them would cost 4 E more registers
     if ((e & 3) == 3) asm volatile("" ::: "memory");
   }
@@ -193,9 +240,15 @@ __global__ __launch_bounds__(MS_THREADS) void k_mala_step(
   // ---- phase 3: new state (mala.py:62-64), every element rewritten (blend, no holes) ----------
   // a chain pair past C stores nowhere: its offset is moved past num_records (dropped by the range check)
   const unsigned woff = cok ? voff : nbytes;
+  // (PC: the slot addresses of grad' formed afresh from an opaque copy of t.  LDS offsets past 64 KiB do not fit an
+  // instruction's offset field, so each slot's address is a register of its own, and kept from phase 1 they are what pushes
+  // the E = 16 instantiation into scratch -- whose reloads here would be vmcnt waits between the stores.  With this and
+  // the same in phase 4: 254 registers, no scratch.)
+  int t3 = t;
+  if (PC) asm volatile("" : "+v"(t3));
 #pragma unroll
   for (int e = 0; e < E; ++e) {
-    const dvec2 q = qs[e * MS_THREADS + t];
+    const dvec2 q = qs[e * MS_THREADS + t3];
     a[e].x = acc0 ? p[e].x : a[e].x;
     a[e].y = acc1 ? p[e].y : a[e].y;
     b[e].x = acc0 ? q.x : b[e].x;
@@ -212,6 +265,10 @@ __global__ __launch_bounds__(MS_THREADS) void k_mala_step(
   // 1 KiB per instruction, and every thread then reads its (chain pair, row) elements transposed.
   // (reads past a chain's D normals land in the row padding / the next chain's row, or past
   // num_records for the last chain -> 0; those LDS cells are never used)
+  // (PC: thread coordinates derived afresh, so that no address of the earlier phases stays live through the decision)
+  int t4 = t;
+  if (PC) asm volatile("" : "+v"(t4));
+  const int j4 = t4 & (MS_PAIRS - 1), r4 = t4 >> 3, lane4 = t4 & (BK_WAVE - 1);
   {
     const unsigned zbytes = (unsigned)(((C - 1) * ldz + D) * 8);
     const __amdgpu_buffer_rsrc_t r_z = __builtin_amdgcn_make_buffer_rsrc((void*)zt, 0, zbytes, BK_RSRC_FLAGS);
@@ -219,22 +276,30 @@ __global__ __launch_bounds__(MS_THREADS) void k_mala_step(
     for (int h = 0; h < 2; ++h) {
       const int cw = 2 * w + h;
       const i64 cc = (cb + cw < C) ? cb + cw : C - 1;
-      const unsigned zoff = (unsigned)(cc * ldz * 8) + 16u * lane;
+      const unsigned zoff = (unsigned)(cc * ldz * 8) + 16u * lane4;
 #pragma unroll
       for (int k = 0; k < (MS_ROWS * E + 127) / 128; ++k)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(r_z, (__attribute__((address_space(3))) void*)(big + (cw * L::ZPITCH + 128 * k) * 8),
                                                  16, zoff, 1024 * k, 0, AUX);
     }
+    // sqrt(v) over 1/v: every thread finished phase 1 two barriers ago
+    if (PC) ms_stage_precond_row<E>(pc + D, D, pcx, w, lane4);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 #pragma unroll
   for (int e = 0; e < E; ++e) {
-    const int d = r + MS_ROWS * e;
-    const double z0 = zs[(2 * j) * L::ZPITCH + d], z1 = zs[(2 * j + 1) * L::ZPITCH + d];
+    const int d = r4 + MS_ROWS * e;
+    const double z0 = zs[(2 * j4) * L::ZPITCH + d], z1 = zs[(2 * j4 + 1) * L::ZPITCH + d];
     dvec2 pn;
-    pn.x = (a[e].x + eps * b[e].x) + s * z0;
-    pn.y = (a[e].y + eps * b[e].y) + s * z1;
+    if (PC) {
+      const double v = pcv[d], sd = pcx[d];
+      pn.x = (a[e].x + eps * (v * b[e].x)) + s * (sd * z0);
+      pn.y = (a[e].y + eps * (v * b[e].y)) + s * (sd * z1);
+    } else {
+      pn.x = (a[e].x + eps * b[e].x) + s * z0;
+      pn.y = (a[e].y + eps * b[e].y) + s * z1;
+    }
     __builtin_amdgcn_raw_buffer_store_b128(as_u4(pn), r_thp, woff, e * slotb, AUX);
   }
 }
@@ -248,10 +313,15 @@ int bk_mala_step_supported(int64_t C, int64_t D, int64_t ld) {
   return (C > 0 && D > 0 && D <= 1024 && C % 2 == 0 && ld % 2 == 0 && ld >= C && D * ld < ((int64_t)1 << 28)) ? 1 : 0;
 }
 
-int bk_mala_step(const double* theta, double* theta_out, double* grad, double* theta_prop,
-                 const double* grad_prop, int64_t ld, double* lp, const double* lp_prop, const double* log_u,
-                 const double* zt_next, int64_t ldz, double eps, double sqrt2eps, uint8_t* accept_mask,
-                 double* ret, uint32_t* accept_count, int64_t C, int64_t D, void* stream) {
+}  // extern "C"
+
+namespace {
+
+template <bool PC>
+int mala_step_launch(const double* theta, double* theta_out, double* grad, double* theta_prop,
+                     const double* grad_prop, int64_t ld, double* lp, const double* lp_prop, const double* log_u,
+                     const double* zt_next, int64_t ldz, double eps, double sqrt2eps, uint8_t* accept_mask,
+                     double* ret, uint32_t* accept_count, int64_t C, int64_t D, const double* precond, void* stream) {
   if (!theta || !theta_out || !grad || !theta_prop || !grad_prop || !lp || !lp_prop || !log_u || C < 0 || D < 0)
     return BK_E_ARG;
   if (C == 0 || D == 0) return BK_OK;
@@ -263,16 +333,16 @@ int bk_mala_step(const double* theta, double* theta_out, double* grad, double* t
   hipStream_t s = bk_stream(stream);
   dim3 grid((unsigned)bk_cdiv(C, MS_CHAINS)), block(MS_THREADS);
   const bool nt = bk_streams_past_llc(6 * C * D);
-#define BK_MS_LAUNCH(E)                                                                                     \
-  do {                                                                                                      \
-    if (nt)                                                                                                 \
-      k_mala_step<E, true><<<grid, block, 0, s>>>(theta, theta_out, grad, theta_prop, grad_prop, ld, lp,   \
-                                                  lp_prop, log_u, zt_next, ldz, eps, sqrt2eps, accept_mask, \
-                                                  ret, accept_count, C, D);                                 \
-    else                                                                                                    \
-      k_mala_step<E, false><<<grid, block, 0, s>>>(theta, theta_out, grad, theta_prop, grad_prop, ld, lp,  \
-                                                   lp_prop, log_u, zt_next, ldz, eps, sqrt2eps,             \
-                                                   accept_mask, ret, accept_count, C, D);                   \
+#define BK_MS_LAUNCH(E)                                                                                         \
+  do {                                                                                                          \
+    if (nt)                                                                                                     \
+      k_mala_step<E, true, PC><<<grid, block, 0, s>>>(theta, theta_out, grad, theta_prop, grad_prop, ld, lp,   \
+                                                      lp_prop, log_u, zt_next, ldz, eps, sqrt2eps, accept_mask, \
+                                                      ret, accept_count, C, D, precond);                        \
+    else                                                                                                        \
+      k_mala_step<E, false, PC><<<grid, block, 0, s>>>(theta, theta_out, grad, theta_prop, grad_prop, ld, lp,  \
+                                                       lp_prop, log_u, zt_next, ldz, eps, sqrt2eps,             \
+                                                       accept_mask, ret, accept_count, C, D, precond);          \
   } while (0)
   if (D <= 128) BK_MS_LAUNCH(2);
   else if (D <= 256) BK_MS_LAUNCH(4);
@@ -280,6 +350,27 @@ int bk_mala_step(const double* theta, double* theta_out, double* grad, double* t
   else BK_MS_LAUNCH(16);
 #undef BK_MS_LAUNCH
   BK_RETURN_LAUNCH_STATUS();
+}
+
+}  // namespace
+
+extern "C" {
+
+int bk_mala_step(const double* theta, double* theta_out, double* grad, double* theta_prop,
+                 const double* grad_prop, int64_t ld, double* lp, const double* lp_prop, const double* log_u,
+                 const double* zt_next, int64_t ldz, double eps, double sqrt2eps, uint8_t* accept_mask,
+                 double* ret, uint32_t* accept_count, int64_t C, int64_t D, void* stream) {
+  return mala_step_launch<false>(theta, theta_out, grad, theta_prop, grad_prop, ld, lp, lp_prop, log_u, zt_next, ldz, eps,
+                                 sqrt2eps, accept_mask, ret, accept_count, C, D, nullptr, stream);
+}
+
+int bk_mala_step_precond(const double* theta, double* theta_out, double* grad, double* theta_prop,
+                         const double* grad_prop, int64_t ld, const double* precond, double* lp, const double* lp_prop,
+                         const double* log_u, const double* zt_next, int64_t ldz, double eps, double sqrt2eps,
+                         uint8_t* accept_mask, double* ret, uint32_t* accept_count, int64_t C, int64_t D, void* stream) {
+  if (!precond) return BK_E_ARG;
+  return mala_step_launch<true>(theta, theta_out, grad, theta_prop, grad_prop, ld, lp, lp_prop, log_u, zt_next, ldz, eps,
+                                sqrt2eps, accept_mask, ret, accept_count, C, D, precond, stream);
 }
 
 }  // extern "C"

@@ -32,18 +32,38 @@ constexpr unsigned RSRC_FLAGS = 0x00020000u;    // raw buffer, 32-bit data forma
 __device__ __forceinline__ dvec2 as_d2(u32x4 v) { return __builtin_bit_cast(dvec2, v); }
 __device__ __forceinline__ u32x4 as_u4(dvec2 v) { return __builtin_bit_cast(u32x4, v); }
 
+// One row of the packed preconditioner (D doubles at `row`) into LDS, as k_mala_step stages it: LDS-DMA, 4 B per lane (rows 1
+// and 2 of the pack are 8-byte aligned only), 256 B per wavefront instruction, the 2 E chunks dealt round robin to the
+// wavefronts; cells of rows >= D receive 0 (range check).
+template <int E, int WAVES>
+__device__ __forceinline__ void stage_precond_row(const double* row, i64 D, double* dst, int w, int lane) {
+  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void*)row, 0, (unsigned)(D * 8), RSRC_FLAGS);
+#pragma unroll
+  for (int k = 0; k < (2 * E + WAVES - 1) / WAVES; ++k) {
+    const int q = w + WAVES * k;  // chunk of 32 doubles
+    if (q < 2 * E)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)(dst + 32 * q), 4,
+                                               4u * lane, 256 * q, 0, 0);
+  }
+}
+
 // E row slots per thread: rows r, r+64, ..., r+64(E-1)  (D <= 64 E)
-template <class TERM, int E, bool NT, int PAIRS>
+// PC: with the packed diagonal preconditioner pc[3][D] = {v, sqrt(v), 1/v} (bk_mala_step_precond's arithmetic and staging: v
+// and 1/v in LDS for phase 1, sqrt(v) over 1/v for phase 4; the built-in Gaussians only -- a generated from-source library
+// instantiates PC = false alone).
+template <class TERM, int E, bool NT, int PAIRS, bool PC = false>
 __global__ __launch_bounds__(64 * PAIRS) void k_mala_step_sep(const double* th, double* out, double* thp, i64 ld,
                                                               const double* params, double* lp,
                                                               const double* __restrict__ lp_p,
                                                               const double* __restrict__ log_u, const double* zt, i64 ldz,
                                                               double eps, double s, uint8_t* mask, double* ret,
-                                                              uint32_t* count, i64 C, i64 D) {
+                                                              uint32_t* count, i64 C, i64 D, const double* pc) {
   constexpr int MS_THREADS = 64 * PAIRS, MS_PAIRS = PAIRS, MS_CHAINS = 2 * PAIRS;
   constexpr int ZPITCH = MS_ROWS * E + 2;  // doubles; +2: conflict-free transposed ds_read_b64
   __shared__ __attribute__((aligned(16))) unsigned char big[MS_CHAINS * ZPITCH * 8];
   __shared__ double red[8 * MS_PAIRS * 4];  // [group of 8 rows][pair][4 sums]
+  __shared__ double pcv[PC ? MS_ROWS * E : 1];  // v
+  __shared__ double pcx[PC ? MS_ROWS * E : 1];  // 1/v in phase 1, sqrt(v) in phase 4
   double* zs = reinterpret_cast<double*>(big);
   constexpr int AUX = NT ? 2 : 0;
 
@@ -66,12 +86,20 @@ __global__ __launch_bounds__(64 * PAIRS) void k_mala_step_sep(const double* th, 
 
   // ---- phase 1: load the block, proposal densities (mala.py:50-53, 68-79) with both gradients recomputed ----------
   dvec2 a[E], p[E];
+  if (PC) {
+    stage_precond_row<E, PAIRS>(pc, D, pcv, w, lane);
+    stage_precond_row<E, PAIRS>(pc + 2 * D, D, pcx, w, lane);
+  }
 #pragma unroll
   for (int e = 0; e < E; ++e) {
     a[e] = as_d2(__builtin_amdgcn_raw_buffer_load_b128(r_th, voff, e * slotb, AUX));
     p[e] = as_d2(__builtin_amdgcn_raw_buffer_load_b128(r_thp, voff, e * slotb, AUX));
   }
   __builtin_amdgcn_sched_barrier(0);
+  if (PC) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the chunks of v and 1/v have landed in LDS (and the block's loads)
+    __syncthreads();
+  }
   double sf0 = 0.0, sf1 = 0.0, sr0 = 0.0, sr1 = 0.0;
 #pragma unroll
   for (int e = 0; e < E; ++e) {
@@ -86,14 +114,27 @@ __global__ __launch_bounds__(64 * PAIRS) void k_mala_step_sep(const double* th, 
     TERM::eval(p[e].x, dd, params, tm, q0);
     TERM::eval(p[e].y, dd, params, tm, q1);
     // x = (theta' - theta) - eps*grad ; reverse: (theta - theta') - eps*grad'   (mala.py:78)
-    const double xf0 = rok ? (p[e].x - a[e].x) - eps * b0 : 0.0;
-    const double xf1 = rok ? (p[e].y - a[e].y) - eps * b1 : 0.0;
-    const double xr0 = rok ? (a[e].x - p[e].x) - eps * q0 : 0.0;
-    const double xr1 = rok ? (a[e].y - p[e].y) - eps * q1 : 0.0;
-    sf0 = sf0 + xf0 * xf0;
-    sf1 = sf1 + xf1 * xf1;
-    sr0 = sr0 + xr0 * xr0;
-    sr1 = sr1 + xr1 * xr1;
+    if (PC) {
+      // x = (theta' - theta) - eps*(v*grad), weighted (x*x)*(1/v); rows >= D: v = 1/v = 0 in LDS, the sums receive +0.0
+      const double v = pcv[d], iv = pcx[d];
+      const double xf0 = rok ? (p[e].x - a[e].x) - eps * (v * b0) : 0.0;
+      const double xf1 = rok ? (p[e].y - a[e].y) - eps * (v * b1) : 0.0;
+      const double xr0 = rok ? (a[e].x - p[e].x) - eps * (v * q0) : 0.0;
+      const double xr1 = rok ? (a[e].y - p[e].y) - eps * (v * q1) : 0.0;
+      sf0 = sf0 + (xf0 * xf0) * iv;
+      sf1 = sf1 + (xf1 * xf1) * iv;
+      sr0 = sr0 + (xr0 * xr0) * iv;
+      sr1 = sr1 + (xr1 * xr1) * iv;
+    } else {
+      const double xf0 = rok ? (p[e].x - a[e].x) - eps * b0 : 0.0;
+      const double xf1 = rok ? (p[e].y - a[e].y) - eps * b1 : 0.0;
+      const double xr0 = rok ? (a[e].x - p[e].x) - eps * q0 : 0.0;
+      const double xr1 = rok ? (a[e].y - p[e].y) - eps * q1 : 0.0;
+      sf0 = sf0 + xf0 * xf0;
+      sf1 = sf1 + xf1 * xf1;
+      sr0 = sr0 + xr0 * xr0;
+      sr1 = sr1 + xr1 * xr1;
+    }
     // (slot by slot: hoisting every slot's parameter loads and gradients would not fit the 256 registers of a thread)
     if ((e & 1) == 1) asm volatile("" ::: "memory");
   }
@@ -185,6 +226,8 @@ __global__ __launch_bounds__(64 * PAIRS) void k_mala_step_sep(const double* th, 
         __builtin_amdgcn_raw_ptr_buffer_load_lds(r_z, (__attribute__((address_space(3))) void*)(big + (cw * ZPITCH + 128 * k) * 8),
                                                  16, zoff, 1024 * k, 0, AUX);
     }
+    // sqrt(v) over 1/v: every thread finished phase 1 two barriers ago
+    if (PC) stage_precond_row<E, PAIRS>(pc + D, D, pcx, w, lane);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -197,19 +240,27 @@ __global__ __launch_bounds__(64 * PAIRS) void k_mala_step_sep(const double* th, 
     TERM::eval(a[e].x, dd, params, tm, b0);
     TERM::eval(a[e].y, dd, params, tm, b1);
     dvec2 pn;
-    pn.x = (a[e].x + eps * b0) + s * z0;
-    pn.y = (a[e].y + eps * b1) + s * z1;
+    if (PC) {
+      const double v = pcv[d], sd = pcx[d];
+      pn.x = (a[e].x + eps * (v * b0)) + s * (sd * z0);
+      pn.y = (a[e].y + eps * (v * b1)) + s * (sd * z1);
+    } else {
+      pn.x = (a[e].x + eps * b0) + s * z0;
+      pn.y = (a[e].y + eps * b1) + s * z1;
+    }
     __builtin_amdgcn_raw_buffer_store_b128(as_u4(pn), r_thp, woff, e * slotb, AUX);
     if ((e & 3) == 3) asm volatile("" ::: "memory");
   }
 }
 
-// Host side: the arguments of bk_mala_step (include/bkhip.h) without the two gradient arrays, plus the density's params.
-template <class TERM>
+// Host side: the arguments of bk_mala_step (include/bkhip.h) without the two gradient arrays, plus the density's params
+// (and, PC, the packed preconditioner).
+template <class TERM, bool PC = false>
 static int mala_step_sep_launch(const double* theta, double* theta_out, double* theta_prop, int64_t ld, const double* params,
                                 double* lp, const double* lp_prop, const double* log_u, const double* zt_next, int64_t ldz,
                                 double eps, double sqrt2eps, uint8_t* accept_mask, double* ret, uint32_t* accept_count,
-                                int64_t C, int64_t D, void* stream) {
+                                int64_t C, int64_t D, void* stream, const double* precond = nullptr) {
+  if (PC && !precond) return BK_E_ARG;
   if (!theta || !theta_out || !theta_prop || !lp || !lp_prop || !log_u || C < 0 || D < 0) return BK_E_ARG;
   if (C == 0 || D == 0) return BK_OK;
   // 32-bit byte offsets inside every array, with headroom for the slot offsets (bk_mala_step_supported)
@@ -220,9 +271,9 @@ static int mala_step_sep_launch(const double* theta, double* theta_out, double* 
   constexpr int P = 8;  // chain pairs per workgroup (the note on PAIRS above)
   const bool nt = bk_streams_past_llc(4 * C * D);
 #define BKM_LAUNCH2(E, NT)                                                                                               \
-  k_mala_step_sep<TERM, E, NT, P><<<dim3((unsigned)bk_cdiv(C, 2 * P)), dim3(64 * P), 0, s>>>(                            \
+  k_mala_step_sep<TERM, E, NT, P, PC><<<dim3((unsigned)bk_cdiv(C, 2 * P)), dim3(64 * P), 0, s>>>(                        \
       theta, theta_out, theta_prop, ld, params, lp, lp_prop, log_u, zt_next, ldz, eps, sqrt2eps, accept_mask, ret, accept_count, C, \
-      D)
+      D, precond)
 #define BKM_LAUNCH(E)             \
   do {                            \
     if (nt) BKM_LAUNCH2(E, true); \

@@ -804,8 +804,11 @@ static void refresh_apply_kin_launch(const double* work, i64 dp, const double* l
 }
 
 // theta' = (theta + eps*grad) + s*z with z already drawn (mala.py:41-45), two rows per thread
+// PC (bk_mala_propose_from_normals_precond): theta' = (theta + eps*(v*grad)) + s*(sqrt(v)*z), pc = the packed {v, sqrt(v), 1/v}
+template <bool PC>
 __global__ __launch_bounds__(256) void k_mala_propose_z(const double* th, const double* g, const double* z,
-                                                        double* prop, i64 ld, double eps, double s, i64 C, i64 D) {
+                                                        double* prop, i64 ld, double eps, double s, i64 C, i64 D,
+                                                        const double* __restrict__ pc) {
   i64 c = (i64)blockIdx.x * 256 + threadIdx.x;
   i64 d0 = (i64)blockIdx.y * 4;
   if (c >= C) return;
@@ -820,14 +823,18 @@ __global__ __launch_bounds__(256) void k_mala_propose_z(const double* th, const 
     }
 #pragma unroll
   for (int i = 0; i < 4; ++i)
-    if (d0 + i < D) prop[(d0 + i) * ld + c] = (a[i] + eps * b[i]) + s * n[i];
+    if (d0 + i < D) {
+      if (PC) prop[(d0 + i) * ld + c] = (a[i] + eps * (pc[d0 + i] * b[i])) + s * (pc[D + d0 + i] * n[i]);
+      else prop[(d0 + i) * ld + c] = (a[i] + eps * b[i]) + s * n[i];
+    }
 }
 
 // the same with the normals chain-major (zt[c*ldz + d], as k_zig_parallel leaves them): 64x64
 // tiles turned through LDS, so both sides stay coalesced
+template <bool PC>
 __global__ __launch_bounds__(256) void k_mala_propose_zt(const double* th, const double* g, const double* zt,
                                                          i64 ldz, double* prop, i64 ld, double eps, double s,
-                                                         i64 C, i64 D) {
+                                                         i64 C, i64 D, const double* __restrict__ pc) {
   __shared__ double tile[64][65];
   i64 c0 = (i64)blockIdx.x * 64, d0 = (i64)blockIdx.y * 64;
   int tx = threadIdx.x & 63, ty = bk_wave_id();
@@ -846,7 +853,8 @@ __global__ __launch_bounds__(256) void k_mala_propose_zt(const double* th, const
     i64 d = d0 + dl;
     if (d < D) {
       i64 o = d * ld + cc;
-      prop[o] = (th[o] + eps * g[o]) + s * tile[tx][dl];
+      if (PC) prop[o] = (th[o] + eps * (pc[d] * g[o])) + s * (pc[D + d] * tile[tx][dl]);
+      else prop[o] = (th[o] + eps * g[o]) + s * tile[tx][dl];
     }
   }
 }
@@ -1108,23 +1116,47 @@ int bk_mala_propose(int rng_kind, uint64_t* state, int64_t ldr, const double* th
   BK_RETURN_LAUNCH_STATUS();
 }
 
-int bk_mala_propose_from_normals(const double* theta, const double* grad, const double* z, int64_t z_stride_d,
-                                 int64_t z_stride_c, double* theta_prop, int64_t ld, double eps,
-                                 double sqrt2eps, int64_t C, int64_t D, void* stream) {
-  if (!theta || !grad || !z || !theta_prop || C < 0 || D < 0) return BK_E_ARG;
+}  // extern "C"
+
+namespace {
+
+template <bool PC>
+int mala_propose_from_normals_launch(const double* theta, const double* grad, const double* z, int64_t z_stride_d,
+                                     int64_t z_stride_c, double* theta_prop, int64_t ld, double eps, double sqrt2eps,
+                                     int64_t C, int64_t D, const double* precond, void* stream) {
+  if (!theta || !grad || !z || !theta_prop || (PC && !precond) || C < 0 || D < 0) return BK_E_ARG;
   if (ld < C) return BK_E_ALIGN;
   if (C == 0 || D == 0) return BK_OK;
   if (z_stride_c == 1 && z_stride_d == ld) {
     dim3 grid((unsigned)bk_cdiv(C, 256), (unsigned)bk_cdiv(D, 4));
-    k_mala_propose_z<<<grid, dim3(256), 0, bk_stream(stream)>>>(theta, grad, z, theta_prop, ld, eps, sqrt2eps, C, D);
+    k_mala_propose_z<PC><<<grid, dim3(256), 0, bk_stream(stream)>>>(theta, grad, z, theta_prop, ld, eps, sqrt2eps, C, D,
+                                                                    precond);
   } else if (z_stride_d == 1 && z_stride_c >= D) {
     dim3 grid((unsigned)bk_cdiv(C, 64), (unsigned)bk_cdiv(D, 64));
-    k_mala_propose_zt<<<grid, dim3(256), 0, bk_stream(stream)>>>(theta, grad, z, z_stride_c, theta_prop, ld, eps,
-                                                                 sqrt2eps, C, D);
+    k_mala_propose_zt<PC><<<grid, dim3(256), 0, bk_stream(stream)>>>(theta, grad, z, z_stride_c, theta_prop, ld, eps,
+                                                                     sqrt2eps, C, D, precond);
   } else {
     return BK_E_ALIGN;
   }
   BK_RETURN_LAUNCH_STATUS();
+}
+
+}  // namespace
+
+extern "C" {
+
+int bk_mala_propose_from_normals(const double* theta, const double* grad, const double* z, int64_t z_stride_d,
+                                 int64_t z_stride_c, double* theta_prop, int64_t ld, double eps,
+                                 double sqrt2eps, int64_t C, int64_t D, void* stream) {
+  return mala_propose_from_normals_launch<false>(theta, grad, z, z_stride_d, z_stride_c, theta_prop, ld, eps, sqrt2eps, C, D,
+                                                 nullptr, stream);
+}
+
+int bk_mala_propose_from_normals_precond(const double* theta, const double* grad, const double* z, int64_t z_stride_d,
+                                         int64_t z_stride_c, const double* precond, double* theta_prop, int64_t ld,
+                                         double eps, double sqrt2eps, int64_t C, int64_t D, void* stream) {
+  return mala_propose_from_normals_launch<true>(theta, grad, z, z_stride_d, z_stride_c, theta_prop, ld, eps, sqrt2eps, C, D,
+                                                precond, stream);
 }
 
 int bk_normals_chain_major(int rng_kind, uint64_t* state, int64_t ldr, double* zt, int64_t ldz, int64_t C,

@@ -299,6 +299,20 @@ int bk_mala_step_gaussian(const double* theta, double* theta_out, double* theta_
                                                      sqrt2eps, accept_mask, ret, accept_count, C, D, stream);
 }
 
+int bk_mala_step_gaussian_precond(const double* theta, double* theta_out, double* theta_prop, int64_t ld, const double* lam,
+                                  const double* precond, double* lp, const double* lp_prop, const double* log_u,
+                                  const double* zt_next, int64_t ldz, double eps, double sqrt2eps, uint8_t* accept_mask,
+                                  double* ret, uint32_t* accept_count, int64_t C, int64_t D, void* stream) {
+  // the same kernel with the packed diagonal preconditioner {v, sqrt(v), 1/v} (bk_mala_step_precond's arithmetic)
+  if (lam)
+    return bkm::mala_step_sep_launch<GaussTerm<true>, true>(theta, theta_out, theta_prop, ld, lam, lp, lp_prop, log_u, zt_next,
+                                                            ldz, eps, sqrt2eps, accept_mask, ret, accept_count, C, D, stream,
+                                                            precond);
+  return bkm::mala_step_sep_launch<GaussTerm<false>, true>(theta, theta_out, theta_prop, ld, lam, lp, lp_prop, log_u, zt_next,
+                                                           ldz, eps, sqrt2eps, accept_mask, ret, accept_count, C, D, stream,
+                                                           precond);
+}
+
 int bk_target_funnel_grad_n(const double* theta, double* grad, double* logp, int64_t ld, int64_t C,
                             int64_t D, const uint32_t* n_dev, void* stream) {
   return bkl::target_launch<FunnelDensity>(theta, grad, logp, ld, nullptr, C, D, n_dev, stream);

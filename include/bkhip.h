@@ -379,6 +379,15 @@ int bk_mala_propose_from_normals(const double* theta, const double* grad, const 
                                  int64_t ld, double eps, double sqrt2eps, int64_t C, int64_t D,
                                  void* stream);
 
+/* The proposal of MALA with a diagonal preconditioner v (extension; plain MALA, mala.py:41-45, on theta / sqrt(v)):
+ *     theta_prop = (theta + eps*(v*grad)) + sqrt2eps * (sqrt(v)*z)
+ * precond: the packed [3][D] = {v, sqrt(v), 1/v} that bk_precond_pack writes; z in either layout, as above.  With v = 1
+ * every added factor is an exact multiplication by 1.0: the same doubles as bk_mala_propose_from_normals. */
+int bk_mala_propose_from_normals_precond(const double* theta, const double* grad, const double* z,
+                                         int64_t z_stride_d, int64_t z_stride_c, const double* precond,
+                                         double* theta_prop, int64_t ld, double eps, double sqrt2eps,
+                                         int64_t C, int64_t D, void* stream);
+
 /* zt[c*ldz + d] = d-th next standard normal of chain c's stream, d = 0..D-1 (what
  * `rng.normal(size=D)` returns, mala.py:44 / hmc.py:56), 16 to 64 lanes of a wavefront per chain,
  * Philox streams only; state advanced exactly as by sequential consumption.  ldz >= D.
@@ -415,6 +424,15 @@ int bk_mala_logq(const double* theta, const double* grad, const double* theta_pr
                  const double* grad_prop, int64_t ld, double eps, double* lp_forward,
                  double* lp_reverse, int64_t C, int64_t D, void* stream);
 
+/* The same densities under a diagonal preconditioner v (mala.py:50-53, 68-79 on theta / sqrt(v); the log-determinant is
+ * the same in both directions and is left out), precond = the packed [3][D] {v, sqrt(v), 1/v} of bk_precond_pack:
+ *     xf_d = (theta_prop - theta) - eps*(v*grad)       lp_forward[c] = (-0.25/eps) * sum_d (xf_d*xf_d) * (1/v)_d
+ *     xr_d = (theta - theta_prop) - eps*(v*grad_prop)  lp_reverse[c] = (-0.25/eps) * sum_d (xr_d*xr_d) * (1/v)_d
+ * every product rounded on its own, the sums in bk_mala_logq's order (four contiguous quarters, ((p0+p1)+p2)+p3). */
+int bk_mala_logq_precond(const double* theta, const double* grad, const double* theta_prop,
+                         const double* grad_prop, int64_t ld, const double* precond, double eps,
+                         double* lp_forward, double* lp_reverse, int64_t C, int64_t D, void* stream);
+
 /* The rest of a MALA draw in ONE pass over HBM (mala.py:50-66), plus the next draw's proposal
  * (mala.py:41-45).  A workgroup owns 16 chains x all D dimensions and keeps them on chip (three
  * arrays in registers, grad_prop in LDS) between the per-chain sums and the select:
@@ -441,6 +459,17 @@ int bk_mala_step(const double* theta, double* theta_out, double* grad, double* t
                  const double* log_u, const double* zt_next, int64_t ldz, double eps,
                  double sqrt2eps, uint8_t* accept_mask, double* ret, uint32_t* accept_count,
                  int64_t C, int64_t D, void* stream);
+
+/* bk_mala_step under a diagonal preconditioner (mala.py:41-66 on theta / sqrt(v)): fwd, rev as bk_mala_logq_precond -- in
+ * THIS kernel's summation order --, the same decision and select, and the next proposal as
+ * bk_mala_propose_from_normals_precond.  precond: the packed [3][D] {v, sqrt(v), 1/v} of bk_precond_pack (required; rows
+ * are staged in LDS, 16 KiB more at D > 512).  Same shapes, checks and traffic as bk_mala_step (+ 24*D bytes of
+ * cache-resident vectors per workgroup); with v = 1 the same draws bit for bit. */
+int bk_mala_step_precond(const double* theta, double* theta_out, double* grad, double* theta_prop,
+                         const double* grad_prop, int64_t ld, const double* precond, double* lp,
+                         const double* lp_prop, const double* log_u, const double* zt_next, int64_t ldz,
+                         double eps, double sqrt2eps, uint8_t* accept_mask, double* ret,
+                         uint32_t* accept_count, int64_t C, int64_t D, void* stream);
 
 /* ---- built-in targets: the "thin C-ABI callback" form of GradModel.log_density_gradient
  * (typing.py:25-27) batched over chains.  grad and/or logp may be NULL (HMC discards lp
@@ -566,6 +595,14 @@ int bk_mala_step_gaussian(const double* theta, double* theta_out, double* theta_
                           double* lp, const double* lp_prop, const double* log_u, const double* zt_next, int64_t ldz,
                           double eps, double sqrt2eps, uint8_t* accept_mask, double* ret, uint32_t* accept_count, int64_t C,
                           int64_t D, void* stream);
+
+/* bk_mala_step_gaussian under a diagonal preconditioner (mala.py:41-66 on theta / sqrt(v)): the arithmetic of
+ * bk_mala_step_precond with both gradients recomputed; precond = the packed [3][D] {v, sqrt(v), 1/v} (required).  Same
+ * draws bit for bit as {bk_target_*_gaussian_grad, bk_mala_step_precond}. */
+int bk_mala_step_gaussian_precond(const double* theta, double* theta_out, double* theta_prop, int64_t ld, const double* lam,
+                                  const double* precond, double* lp, const double* lp_prop, const double* log_u,
+                                  const double* zt_next, int64_t ldz, double eps, double sqrt2eps, uint8_t* accept_mask,
+                                  double* ret, uint32_t* accept_count, int64_t C, int64_t D, void* stream);
 
 /* One whole delayed-rejection proposal (drghmc.py:319-346 -> :253-289) on Neal's funnel in a
  * single launch, gradient callback inlined: chain j of the outputs starts from chain
