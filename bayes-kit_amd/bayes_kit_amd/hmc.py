@@ -76,7 +76,6 @@ class HMCDiag(ManyChainSampler):
         if precond_diag is not None and (metric_diag is not None or metric_dense is not None):
             raise ValueError("give precond_diag or metric_diag / metric_dense, not both")
         self._setup(model, metric_diag, init, seed, chains, chain_id0, ops)
-        self._chain_tile = self._pick_tile(chain_tile)
         # Dense metric (extension; the reference only has metric_diag, and its literal
         # semantics -- rho ~ N(0, I), kick with m*grad, kinetic rho.(m*rho) -- leave the target
         # invariant only for m = 1).  The dense form is the proper
@@ -119,6 +118,7 @@ class HMCDiag(ManyChainSampler):
         # ... and ONE launch per trajectory where it has bk_leapfrog_trajectory (a per-chain density compiled from source:
         # theta in registers, rho in LDS through all L steps), followed by the library's finish launch
         self._traj_hook = (bool(fuse_builtin) and self._step_hook and hasattr(model, "bk_leapfrog_trajectory"))
+        self._chain_tile = self._pick_tile(chain_tile)
         self._fused_zt = self._fused_draw and self._rng_kind == _lib.RNG_PHILOX and self._dim >= 32
         D, C, dev = self._dim, self._C, self._ops.device
         f64 = dict(dtype=torch.float64, device=dev)
@@ -300,13 +300,41 @@ class HMCDiag(ManyChainSampler):
     # -- optional cache blocking ----------------------------------------------------------------
     # chain_tile=T runs the L steps tile by tile over blocks of T chains (chains are
     # independent, so this is only a schedule).  The idea: keep a tile's three arrays inside
-    # the 256 MiB Infinity Cache.  Measured on MI355X (config 3, T = 8192): the kernels gain
-    # ~5 % from the cache but 8x more, 8x smaller launches lose more than that
-    # (8.1e7 vs 9.8e7 steps/s), so the default is NO tiling; the knob stays for experiments.
+    # the 256 MiB Infinity Cache: theta, rho and the gradient of T chains, the arrays the in-place
+    # steady-state step touches (the library's own rule for "fits", bk_streams_past_llc of
+    # csrc/bk_common.hpp, is LLC_BYTES).  Inside the cache kick+drift and the gradient op take their
+    # plain variants and a tile-step costs less than an eighth of the full-size step
+    # (profiles/cache_tiles.md).  The default tiles where that applies and pays:
+    #   * only the step-by-step loop with a separate gradient op (a whole-draw, whole-trajectory or
+    #     one-launch-per-step kernel keeps its state on chip or streams it once per step anyway),
+    #   * only when the three arrays are at least TWICE the threshold (two full tiles): just past it most of an untiled
+    #     step still hits the cache and the ragged second tile loses -- 12,288 x 1,024 tiled as 8,192 + 4,096 takes 7.15 ms
+    #     per draw against 6.90 untiled, while 16,384 gains 6 % and 65,538 (eight tiles and one of two chains) 4-5 %,
+    #   * the largest even tile whose three arrays fit (8,192 chains at D = 1,024),
+    #   * and not below MIN_TILE chains: at D = 1,024 tiles of 4,096 and 2,048 chains are SLOWER than no tiling
+    #     (40.7 and 40.0 ms per draw against 38.8; 8,192: 37.8 -- the sweep in the same file): their launches are too
+    #     short to run at the cache's rate.  A larger D would give the fitting tile fewer chains; nobody has measured that.
+    # All of this was measured with the built-in diagonal Gaussian at D = 1,024 and 8,192 to 65,538 chains only: a smaller D
+    # (longer rows, the same bytes per tile) and heavier gradient ops follow the same rule unmeasured.
+    # An explicit chain_tile wins; chain_tile <= 0 means no tiling.
+    LLC_BYTES = 192 << 20
+    MIN_TILE = 8192
+
+    @classmethod
+    def default_chain_tile(cls, C, D):
+        """Chains per tile for C chains of D dimensions on the step-by-step loop; C itself: no tiling."""
+        t = cls.LLC_BYTES // (3 * 8 * D)
+        t -= t % 2
+        return t if t >= cls.MIN_TILE and C >= 2 * t else C
+
     def _pick_tile(self, chain_tile):
         C = self._C
         if chain_tile is None:
-            return C
+            # (bk_eval: a gradient op that writes the tile's gradient array itself; what a PyTorch model allocates on
+            # the way is not among the three arrays, and a dense metric's products are whole-array GEMMs)
+            opaque_loop = (self._batched and self._M is None and hasattr(self._model, "bk_eval")
+                           and not self._fused_draw and not self._lanes_traj and not self._step_hook)
+            return self.default_chain_tile(C, self._dim) if opaque_loop else C
         t = int(chain_tile)
         return C if t <= 0 or t >= C else max(2, t - t % 2)
 

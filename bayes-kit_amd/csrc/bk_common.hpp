@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <initializer_list>
+
 #include "../../include/bkhip.h"
 #include "../../include/bkhip_math.h"
 
@@ -25,6 +27,19 @@ static inline bool bk_aligned16(const void* p) { return (reinterpret_cast<uintpt
 // Whether a kernel touching `elems` doubles streams well past the 256 MiB Infinity Cache
 // (then non-temporal accesses pay) or can be served from it (then they hurt).
 static inline bool bk_streams_past_llc(i64 elems) { return elems * 8 > ((i64)192 << 20); }
+
+// How many DIFFERENT arrays a launch touches: the footprint that competes for the cache counts an array once, however
+// many roles it plays (an in-place call passes the same pointer as input and output); null pointers count nothing.
+// bk_streams_past_llc(bk_distinct_arrays({...}) * C * D) is the rule of every kernel whose arrays may alias.
+static inline i64 bk_distinct_arrays(std::initializer_list<const void*> arrays) {
+  i64 n = 0;
+  for (const void* const* p = arrays.begin(); p != arrays.end(); ++p) {
+    bool seen = *p == nullptr;
+    for (const void* const* q = arrays.begin(); q != p && !seen; ++q) seen = *q == *p;
+    if (!seen) ++n;
+  }
+  return n;
+}
 
 // Index of the calling wavefront inside its workgroup AS A SCALAR: threadIdx.x / 64 is the same for
 // all 64 lanes, but the compiler only knows that if told -- otherwise every loop bound, row guard and

@@ -616,7 +616,12 @@ int bk_leapfrog_kick_drift(const double* theta_in, double* theta_out, const doub
     if (vec) {
       // Streams much larger than the 256 MiB Infinity Cache use non-temporal loads/stores
       // (measured +8 % on MI355X: 6.49 vs 6.0 TB/s); cache-resident tiles use plain
-      // accesses (7.1 TB/s out of the Infinity Cache).
+      // accesses, one row per thread (the best of rows {1, 2, 4} x workgroups of {256, 512, 1024} threads x
+      // {one workgroup per unit, a persistent grid}: profiles/cache_tiles.md).  The footprint is that of the
+      // DIFFERENT arrays: the steady-state step is in place (theta_in == theta_out, rho_in == rho_out), three
+      // arrays -- a tile of 8,192 chains x 1,024 dimensions is 192 MiB and stays in the cache between its
+      // kick+drift and its gradient op, which non-temporal accesses would defeat (+1.5 to +4 us of 70 per step).
+      const i64 arrays = bk_distinct_arrays({theta_in, theta_out, rho_in, rho_out, grad});
 #define BK_KD_LAUNCH(ROWS, NT)                                                                          \
   do {                                                                                                  \
     dim3 grid((unsigned)bk_cdiv(C / 2, KD_BLOCK), (unsigned)bk_cdiv(D, ROWS));                          \
@@ -624,10 +629,13 @@ int bk_leapfrog_kick_drift(const double* theta_in, double* theta_out, const doub
                                                               grad, ldg_d, metric, eps, use_pre, pre,   \
                                                               use_kick, kick, C / 2, D);                \
   } while (0)
-      if (bk_streams_past_llc(5 * C * D))
+      // (one row per thread puts D into gridDim.y: past its limit the plain launch takes two rows as well)
+      if (bk_streams_past_llc(arrays * C * D))
         BK_KD_LAUNCH(2, true);
-      else
+      else if (D <= 65535)
         BK_KD_LAUNCH(1, false);
+      else
+        BK_KD_LAUNCH(2, false);
 #undef BK_KD_LAUNCH
       BK_RETURN_LAUNCH_STATUS();
     }

@@ -599,6 +599,9 @@ static void zig_parallel_launch(uint64_t* state, i64 ldr, double* zt, i64 ldz, i
   i64 n_wg = bk_cdiv(C, chains_per_wg);
   if (max_workgroups > 0 && n_wg > max_workgroups) n_wg = max_workgroups;
   dim3 grid((unsigned)n_wg), block(ZP_WAVES * BK_WAVE);
+  // (The normals are stored with PLAIN stores whatever the size of zt: a lane's 8-byte stores land wherever the stream
+  // puts its dimensions, and as non-temporal stores -- tried so that a 512 MiB scratch would not push cache-resident chain
+  // tiles out of the last-level cache -- they take the launch from 350 to 970 us at 65,536 x 1,024: profiles/cache_tiles.md.)
   if (lpc == 16) k_zig_parallel<16><<<grid, block, 0, s>>>(state, ldr, zt, ldz, C, D, snap);
   else if (lpc == 32) k_zig_parallel<32><<<grid, block, 0, s>>>(state, ldr, zt, ldz, C, D, snap);
   else k_zig_parallel<64><<<grid, block, 0, s>>>(state, ldr, zt, ldz, C, D, snap);
@@ -651,7 +654,8 @@ struct DrBegin {
 
 constexpr int RK_CH = 16;  // dimensions per piece
 
-template <bool BEGIN, bool PD = false>
+// NT: zt is read and out written non-temporally (both stream past the last-level cache: refresh_apply_kin_launch).
+template <bool BEGIN, bool PD = false, bool NT = false>
 __global__ __launch_bounds__(256) void k_refresh_apply_kin(const double* zt, i64 ldz, const double* loc_in,
                                                            double loc_mul, double scale, double* out, i64 ld,
                                                            const double* metric, double* kin_out, i64 C, i64 D,
@@ -674,7 +678,7 @@ __global__ __launch_bounds__(256) void k_refresh_apply_kin(const double* zt, i64
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       i64 cc = c0 + 4 * i + sub, d = d0 + dl;
-      z[i] = (cc < C && d < dhi) ? zt[cc * ldz + d] : 0.0;
+      z[i] = (cc < C && d < dhi) ? (NT ? __builtin_nontemporal_load(zt + cc * ldz + d) : zt[cc * ldz + d]) : 0.0;
     }
     double loc[RK_CH];
 #pragma unroll
@@ -688,7 +692,8 @@ __global__ __launch_bounds__(256) void k_refresh_apply_kin(const double* zt, i64
       if (c < C && d0 + u < dhi) {
         double lo = loc_in ? loc[u] * loc_mul : 0.0;
         double v = lo + (PD ? metric[D + d0 + u] : scale) * tile[w][lane][u];
-        out[(d0 + u) * ld + c] = v;
+        if (NT) __builtin_nontemporal_store(v, out + (d0 + u) * ld + c);
+        else out[(d0 + u) * ld + c] = v;
         double mv = PD ? metric[2 * D + d0 + u] * v : (metric ? metric[d0 + u] * v : v);
         kin = kin + v * mv;
       }
@@ -798,6 +803,9 @@ static void refresh_apply_kin_launch(const double* work, i64 dp, const double* l
   if (dp <= 128 && lds <= 65536)
     k_refresh_apply_kin_rows<BEGIN, PD><<<dim3((unsigned)bk_cdiv(C, 64)), dim3(256), lds, s>>>(work, dp, loc_in, loc_mul, scale,
                                                                                           out, ld, metric, kin_out, C, D, b);
+  else if (bk_streams_past_llc(bk_distinct_arrays({work, out, loc_in}) * C * D))
+    k_refresh_apply_kin<BEGIN, PD, true><<<dim3((unsigned)bk_cdiv(C, 64)), dim3(256), 0, s>>>(work, dp, loc_in, loc_mul, scale,
+                                                                                         out, ld, metric, kin_out, C, D, b);
   else
     k_refresh_apply_kin<BEGIN, PD><<<dim3((unsigned)bk_cdiv(C, 64)), dim3(256), 0, s>>>(work, dp, loc_in, loc_mul, scale, out,
                                                                                    ld, metric, kin_out, C, D, b);

@@ -207,10 +207,16 @@ int gauss(const double* theta, double* grad, double* logp, i64 ld, const double*
   }
   if (D == 0) return BK_OK;
   if (C % 2 == 0 && ld % 2 == 0 && bk_aligned16(theta) && bk_aligned16(grad)) {
-    if (bk_streams_past_llc(2 * C * D) && D <= 65535) {
-      // one row per thread, non-temporal: 6.5 TB/s vs 6.1 with four rows (MI355X, 1 GiB streams)
+    const bool streams = bk_streams_past_llc(bk_distinct_arrays({theta, grad}) * C * D);
+    if (D <= 65535) {
+      // one row per thread.  Past the cache non-temporal: 6.5 TB/s vs 6.1 with four rows (MI355X, 1 GiB streams).  Inside
+      // it plain: after a kick+drift that left the tile in the cache, 19.9 us at 8,192 x 1,024 against 20.5 with two rows
+      // (rows {1, 2, 4} x workgroups of {256, 512, 1024} x {one workgroup per unit, persistent}: profiles/cache_tiles.md).
+      // Non-temporal is another 0.8 us faster there but 9 us slower behind a non-temporal kick+drift, and this op does
+      // not know its producer.
       dim3 grid((unsigned)bk_cdiv(C / 2, TG_BLOCK), (unsigned)D);
-      k_gauss_grad_v2<1, true><<<grid, dim3(TG_BLOCK), 0, s>>>(theta, grad, ld, lam, C / 2, D);
+      if (streams) k_gauss_grad_v2<1, true><<<grid, dim3(TG_BLOCK), 0, s>>>(theta, grad, ld, lam, C / 2, D);
+      else k_gauss_grad_v2<1, false><<<grid, dim3(TG_BLOCK), 0, s>>>(theta, grad, ld, lam, C / 2, D);
     } else {
       dim3 grid((unsigned)bk_cdiv(C / 2, TG_BLOCK), (unsigned)bk_cdiv(D, 2));
       k_gauss_grad_v2<2, false><<<grid, dim3(TG_BLOCK), 0, s>>>(theta, grad, ld, lam, C / 2, D);

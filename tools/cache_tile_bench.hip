@@ -1,0 +1,268 @@
+// Stand-alone measurement behind profiles/cache_tiles.md: shapes of kick+drift (bk_integrator.hip: k_kick_drift_v2) and of
+// the Gaussian gradient op (bk_targets.hip: k_gauss_grad_v2) on one Infinity-Cache tile.  A trajectory's worth of launches --
+// 64 alternating (kick+drift, gradient) pairs, in place, on columns [0, C) of a [D][ld] state -- timed by HIP events, for
+// every pair of the variants listed below; the kernels are copies of the library's with the shape as template arguments.
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off tools/cache_tile_bench.hip -o cache_tile_bench
+//   cache_tile_bench C D ld              every pair (a tile of a 65,536-chain state: 8192 1024 65536)
+//   cache_tile_bench C D ld KD G         one pair, e.g. under rocprofv3 --kernel-trace --stats
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <algorithm>
+#include <vector>
+
+typedef int64_t i64;
+typedef double dvec2 __attribute__((ext_vector_type(2)));
+
+#define CHECK(x)                                                                  \
+  do {                                                                            \
+    hipError_t e_ = (x);                                                          \
+    if (e_ != hipSuccess) {                                                       \
+      fprintf(stderr, "%s:%d %s\n", __FILE__, __LINE__, hipGetErrorString(e_));   \
+      exit(2);                                                                    \
+    }                                                                             \
+  } while (0)
+
+__device__ __forceinline__ double kd_elem(double th, double rho, double g, double m, bool has_m, double eps, int use_pre,
+                                          double pre, int use_kick, double kick, double& rho_new) {
+  double t = has_m ? m * g : g;
+  double r = rho;
+  if (use_pre) r = r + pre * t;
+  if (use_kick) r = r + kick * t;
+  rho_new = r;
+  return th + eps * r;
+}
+
+template <int ROWS, int NT>
+__device__ __forceinline__ void kd_unit(i64 c2, i64 d0, const double* th_in, double* th_out, const double* rho_in,
+                                        double* rho_out, i64 ld, const double* grad, i64 ldg, const double* metric,
+                                        double eps, int use_pre, double pre, int use_kick, double kick, i64 C2, i64 D) {
+  if (c2 >= C2) return;
+  dvec2 t[ROWS], r[ROWS], g[ROWS];
+  double m[ROWS];
+#pragma unroll
+  for (int i = 0; i < ROWS; ++i) {
+    i64 d = d0 + i;
+    if (d < D) {
+      const dvec2* pt = reinterpret_cast<const dvec2*>(th_in + d * ld + 2 * c2);
+      const dvec2* pr = reinterpret_cast<const dvec2*>(rho_in + d * ld + 2 * c2);
+      const dvec2* pg = reinterpret_cast<const dvec2*>(grad + d * ldg + 2 * c2);
+      if (NT & 1) {
+        t[i] = __builtin_nontemporal_load(pt);
+        r[i] = __builtin_nontemporal_load(pr);
+        g[i] = __builtin_nontemporal_load(pg);
+      } else {
+        t[i] = *pt;
+        r[i] = *pr;
+        g[i] = *pg;
+      }
+      m[i] = metric ? metric[d] : 1.0;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < ROWS; ++i) {
+    i64 d = d0 + i;
+    if (d < D) {
+      dvec2 rn, tn;
+      double rx, ry;
+      tn.x = kd_elem(t[i].x, r[i].x, g[i].x, m[i], metric != nullptr, eps, use_pre, pre, use_kick, kick, rx);
+      tn.y = kd_elem(t[i].y, r[i].y, g[i].y, m[i], metric != nullptr, eps, use_pre, pre, use_kick, kick, ry);
+      rn.x = rx;
+      rn.y = ry;
+      dvec2* qr = reinterpret_cast<dvec2*>(rho_out + d * ld + 2 * c2);
+      dvec2* qt = reinterpret_cast<dvec2*>(th_out + d * ld + 2 * c2);
+      if (NT & 2) {
+        __builtin_nontemporal_store(rn, qr);
+        __builtin_nontemporal_store(tn, qt);
+      } else {
+        *qr = rn;
+        *qt = tn;
+      }
+    }
+  }
+}
+
+// PERSIST: grid of gridDim.x workgroups walks the (chain block, row group) units in launch order
+template <int ROWS, int NT, int BLOCK, bool PERSIST>
+__global__ __launch_bounds__(BLOCK) void k_kd(const double* th_in, double* th_out, const double* rho_in, double* rho_out,
+                                              i64 ld, const double* grad, i64 ldg, const double* metric, double eps,
+                                              int use_pre, double pre, int use_kick, double kick, i64 C2, i64 D) {
+  if (PERSIST) {
+    const i64 nx = (C2 + BLOCK - 1) / BLOCK, ny = (D + ROWS - 1) / ROWS;
+    for (i64 u = blockIdx.x; u < nx * ny; u += gridDim.x)
+      kd_unit<ROWS, NT>((u % nx) * BLOCK + threadIdx.x, (u / nx) * ROWS, th_in, th_out, rho_in, rho_out, ld, grad, ldg,
+                        metric, eps, use_pre, pre, use_kick, kick, C2, D);
+  } else {
+    kd_unit<ROWS, NT>((i64)blockIdx.x * BLOCK + threadIdx.x, (i64)blockIdx.y * ROWS, th_in, th_out, rho_in, rho_out, ld,
+                      grad, ldg, metric, eps, use_pre, pre, use_kick, kick, C2, D);
+  }
+}
+
+template <int ROWS, int NT>
+__device__ __forceinline__ void g_unit(i64 c2, i64 d0, const double* th, double* g, i64 ld, const double* lam, i64 C2,
+                                       i64 D) {
+  if (c2 >= C2) return;
+  dvec2 t[ROWS];
+  double l[ROWS];
+#pragma unroll
+  for (int i = 0; i < ROWS; ++i)
+    if (d0 + i < D) {
+      const dvec2* p = reinterpret_cast<const dvec2*>(th + (d0 + i) * ld + 2 * c2);
+      t[i] = (NT & 1) ? __builtin_nontemporal_load(p) : *p;
+      l[i] = lam ? lam[d0 + i] : 1.0;
+    }
+#pragma unroll
+  for (int i = 0; i < ROWS; ++i)
+    if (d0 + i < D) {
+      dvec2 o;
+      o.x = lam ? -(l[i] * t[i].x) : -t[i].x;
+      o.y = lam ? -(l[i] * t[i].y) : -t[i].y;
+      dvec2* q = reinterpret_cast<dvec2*>(g + (d0 + i) * ld + 2 * c2);
+      if (NT & 2) __builtin_nontemporal_store(o, q);
+      else *q = o;
+    }
+}
+
+template <int ROWS, int NT, int BLOCK, bool PERSIST>
+__global__ __launch_bounds__(BLOCK) void k_g(const double* th, double* g, i64 ld, const double* lam, i64 C2, i64 D) {
+  if (PERSIST) {
+    const i64 nx = (C2 + BLOCK - 1) / BLOCK, ny = (D + ROWS - 1) / ROWS;
+    for (i64 u = blockIdx.x; u < nx * ny; u += gridDim.x)
+      g_unit<ROWS, NT>((u % nx) * BLOCK + threadIdx.x, (u / nx) * ROWS, th, g, ld, lam, C2, D);
+  } else {
+    g_unit<ROWS, NT>((i64)blockIdx.x * BLOCK + threadIdx.x, (i64)blockIdx.y * ROWS, th, g, ld, lam, C2, D);
+  }
+}
+
+struct Args {
+  double *th, *rho, *g, *lam;
+  i64 ld, C, D;
+  hipStream_t s;
+};
+
+static i64 cdiv(i64 a, i64 b) { return (a + b - 1) / b; }
+constexpr int PGRID = 256 * 8;  // persistent: 8 workgroups per CU
+
+template <int ROWS, int NT, int BLOCK, bool PERSIST>
+static void launch_kd(const Args& a) {
+  dim3 grid = PERSIST ? dim3(PGRID) : dim3((unsigned)cdiv(a.C / 2, BLOCK), (unsigned)cdiv(a.D, ROWS));
+  k_kd<ROWS, NT, BLOCK, PERSIST><<<grid, dim3(BLOCK), 0, a.s>>>(a.th, a.th, a.rho, a.rho, a.ld, a.g, a.ld, nullptr, 0.01, 0,
+                                                                 0.0, 1, 0.01, a.C / 2, a.D);
+}
+template <int ROWS, int NT, int BLOCK, bool PERSIST>
+static void launch_g(const Args& a) {
+  dim3 grid = PERSIST ? dim3(PGRID) : dim3((unsigned)cdiv(a.C / 2, BLOCK), (unsigned)cdiv(a.D, ROWS));
+  k_g<ROWS, NT, BLOCK, PERSIST><<<grid, dim3(BLOCK), 0, a.s>>>(a.th, a.g, a.ld, a.lam, a.C / 2, a.D);
+}
+
+struct Variant {
+  const char* name;
+  void (*fn)(const Args&);
+};
+
+#define V(f, R, N, B, P) {#f "<" #R "," #N "," #B "," #P ">", &f<R, N, B, P>}
+// <rows per thread, non-temporal: 1 loads | 2 stores, threads per workgroup, persistent grid>
+static const Variant KD[] = {
+    V(launch_kd, 2, 3, 256, false),  // 0: the streaming variant (what the library launched at this shape before)
+    V(launch_kd, 1, 0, 256, false),  // 1: the library's plain variant
+    V(launch_kd, 1, 1, 256, false),  V(launch_kd, 1, 2, 256, false),  V(launch_kd, 2, 2, 256, false),
+    V(launch_kd, 2, 0, 256, false),  V(launch_kd, 4, 0, 256, false),  V(launch_kd, 1, 0, 512, false),
+    V(launch_kd, 2, 0, 512, false),  V(launch_kd, 1, 0, 1024, false), V(launch_kd, 2, 0, 1024, false),
+    V(launch_kd, 1, 0, 256, true),   V(launch_kd, 2, 0, 256, true),   V(launch_kd, 4, 0, 256, true),
+    V(launch_kd, 2, 0, 512, true),   V(launch_kd, 2, 3, 256, true),
+};
+static const Variant G[] = {
+    V(launch_g, 2, 0, 256, false),  // 0: the library's plain variant before
+    V(launch_g, 1, 3, 256, false),  // 1: the library's streaming variant
+    V(launch_g, 1, 2, 256, false),  V(launch_g, 1, 1, 256, false), V(launch_g, 2, 2, 256, false),
+    V(launch_g, 2, 3, 256, false),  V(launch_g, 1, 0, 256, false),  // 6: the library's plain variant now
+    V(launch_g, 4, 2, 256, false),  V(launch_g, 4, 0, 256, false), V(launch_g, 2, 0, 512, false),
+    V(launch_g, 2, 0, 1024, false), V(launch_g, 2, 0, 256, true),  V(launch_g, 4, 0, 256, true),
+    V(launch_g, 2, 0, 512, true),
+};
+constexpr int NKD = sizeof(KD) / sizeof(KD[0]), NG = sizeof(G) / sizeof(G[0]);
+
+__global__ void k_fill(double* p, i64 n, double v) {
+  for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (i64)gridDim.x * blockDim.x) p[i] = v + 1e-9 * (double)(i & 1023);
+}
+
+constexpr int L = 64;
+
+// one trajectory's worth of launches, `reps` times after one warm-up trajectory: out = {median, min, max} ms per trajectory
+static void run_pair(const Args& a, int ik, int ig, int reps, double out[3]) {
+  hipEvent_t e0, e1;
+  CHECK(hipEventCreate(&e0));
+  CHECK(hipEventCreate(&e1));
+  std::vector<float> tot;
+  for (int r = 0; r < reps + 1; ++r) {
+    CHECK(hipEventRecord(e0, a.s));
+    for (int n = 0; n < L; ++n) {
+      KD[ik].fn(a);
+      G[ig].fn(a);
+    }
+    CHECK(hipEventRecord(e1, a.s));
+    CHECK(hipEventSynchronize(e1));
+    CHECK(hipGetLastError());
+    float ms;
+    CHECK(hipEventElapsedTime(&ms, e0, e1));
+    if (r) tot.push_back(ms);
+  }
+  std::sort(tot.begin(), tot.end());
+  out[0] = tot[tot.size() / 2];
+  out[1] = tot.front();
+  out[2] = tot.back();
+  CHECK(hipEventDestroy(e0));
+  CHECK(hipEventDestroy(e1));
+}
+
+int main(int argc, char** argv) {
+  if (argc < 4) {
+    fprintf(stderr, "usage: cache_tile_bench C D ld [kd g]\n");
+    return 1;
+  }
+  Args a;
+  a.C = atoll(argv[1]);
+  a.D = atoll(argv[2]);
+  a.ld = atoll(argv[3]);
+  if (a.C % 2 || a.ld % 2 || a.ld < a.C || a.C <= 0 || a.D <= 0) return 1;
+  CHECK(hipStreamCreate(&a.s));
+  const i64 n = a.D * a.ld;
+  CHECK(hipMalloc(&a.th, n * 8));
+  CHECK(hipMalloc(&a.rho, n * 8));
+  CHECK(hipMalloc(&a.g, n * 8));
+  CHECK(hipMalloc(&a.lam, a.D * 8));
+  k_fill<<<1024, 256, 0, a.s>>>(a.th, n, 0.5);
+  k_fill<<<1024, 256, 0, a.s>>>(a.rho, n, 0.25);
+  k_fill<<<1024, 256, 0, a.s>>>(a.g, n, 0.125);
+  k_fill<<<4, 256, 0, a.s>>>(a.lam, a.D, 1.0);
+  CHECK(hipStreamSynchronize(a.s));
+  const double bytes = (double)L * 56.0 * (double)a.C * (double)a.D;
+  double o[3];
+  if (argc >= 6) {  // one pair, for a kernel trace
+    int ik = atoi(argv[4]), ig = atoi(argv[5]);
+    if (ik < 0 || ik >= NKD || ig < 0 || ig >= NG) return 1;
+    run_pair(a, ik, ig, 5, o);
+    printf("PAIR C=%lld D=%lld ld=%lld %s + %s: median %.4f ms per %d steps (min %.4f max %.4f) = %.1f us/step %.2f TB/s\n",
+           (long long)a.C, (long long)a.D, (long long)a.ld, KD[ik].name, G[ig].name, o[0], L, o[1], o[2], o[0] * 1e3 / L,
+           bytes / (o[0] * 1e-3) / 1e12);
+    return 0;
+  }
+  double best = 1e30;
+  int bk = 0, bg = 0;
+  for (int ik = 0; ik < NKD; ++ik)
+    for (int ig = 0; ig < NG; ++ig) {
+      run_pair(a, ik, ig, 7, o);
+      printf("SWEEP C=%lld ld=%lld kd=%d g=%d %-32s + %-30s median %.1f us/step (min %.1f max %.1f) %.2f TB/s\n",
+             (long long)a.C, (long long)a.ld, ik, ig, KD[ik].name, G[ig].name, o[0] * 1e3 / L, o[1] * 1e3 / L,
+             o[2] * 1e3 / L, bytes / (o[0] * 1e-3) / 1e12);
+      if (o[0] < best) best = o[0], bk = ik, bg = ig;
+    }
+  // the reference pair again at the end: drift of the box over the sweep
+  run_pair(a, 0, 0, 7, o);
+  printf("SWEEP C=%lld ld=%lld kd=0 g=0 (again) median %.1f us/step (min %.1f max %.1f)\n", (long long)a.C, (long long)a.ld,
+         o[0] * 1e3 / L, o[1] * 1e3 / L, o[2] * 1e3 / L);
+  printf("BEST %d %d %.1f us/step\n", bk, bg, best * 1e3 / L);
+  return 0;
+}
