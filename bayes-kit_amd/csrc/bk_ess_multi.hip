@@ -414,8 +414,9 @@ int bk_ess_indicator(const double* x, int64_t ld, int64_t n, int64_t C, double q
 
 int bk_select_ranks(const double* rank, const double* values, int64_t n, const double* targets, int64_t k, double* out,
                     void* stream) {
-  if (!rank || !values || !targets || !out || n < 0 || k < 1 || k > 8) return BK_E_ARG;
-  if (n == 0) return BK_OK;
+  if (!targets || !out || n < 0 || k < 1 || k > 8) return BK_E_ARG;
+  if (n == 0) return BK_OK;  // (a rank without chains: its empty arrays may come as null pointers)
+  if (!rank || !values) return BK_E_ARG;
   k_select_ranks<<<dim3((unsigned)bk_cdiv(n, EM_BLOCK)), dim3(EM_BLOCK), 0, bk_stream(stream)>>>(rank, values, n, targets,
                                                                                                 (int)k, out);
   BK_RETURN_LAUNCH_STATUS();

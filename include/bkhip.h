@@ -914,7 +914,8 @@ int bk_ess_acov_sums(const double* acor, int64_t ldo, int64_t n, int64_t C, cons
 /* out[t*ldo + c] = (x[t*ld + c] <= q) ? 1 : 0, t < n: the indicator chains for the FFT route of tail ESS. */
 int bk_ess_indicator(const double* x, int64_t ld, int64_t n, int64_t C, double q, double* out, int64_t ldo, void* stream);
 /* Order statistics by global rank (the quantile of tail ESS across ranks): out[j] = values[i] for the element whose 1-based
- * rank[i] equals targets[j], j < k <= 8; other entries of out are left alone (zero them, then sum over ranks). */
+ * rank[i] equals targets[j], j < k <= 8; other entries of out are left alone (zero them, then sum over ranks).  n = 0 (a rank
+ * without chains) returns BK_OK without a launch, whatever rank and values point to. */
 int bk_select_ranks(const double* rank, const double* values, int64_t n, const double* targets, int64_t k, double* out,
                     void* stream);
 

@@ -97,7 +97,7 @@ def ess_mean(x, direct=False):
 
 
 def ess_bulk(x):
-    if not np.all(np.isfinite(x)):
+    if not np.all(np.isfinite(split_rows(x))):  # (the split set: the middle row of an odd N is not part of the estimator)
         return np.nan
     return ess_split_chains(split(z_scores(x)))[0]
 
@@ -139,6 +139,8 @@ class MultiEssFakeOps(FakeOps):
         super().__init__()
         self.max_half = max_half
 
+    # Every entry point takes what the HIP wrappers take: strided [:, off:off + C] views of wider buffers and the leading
+    # entries of longer (NaN-padded) vectors; only the cells of the views are read or written.
     @staticmethod
     def _split(x, q):
         a = x.numpy()
@@ -153,34 +155,41 @@ class MultiEssFakeOps(FakeOps):
     def ess_split_moments(self, x, q, chain_mean, chain_g0):
         self._count("ess_split_moments")
         a, s = self._split(x, q)
-        n = s.shape[0]
-        mu = s.mean(axis=0)
-        g0 = ((s - mu) ** 2).sum(axis=0) / n
-        chain_mean.numpy()[...] = mu
-        chain_g0.numpy()[...] = g0
-        bad = float(np.sum(~np.isfinite(split(a))))
-        return torch.tensor([mu.sum(), g0.sum(), bad], dtype=torch.float64)
+        n, M = s.shape
+        with np.errstate(invalid="ignore", over="ignore"):  # (a non-finite draw makes its chain's moments NaN, as on the device)
+            mu = s.sum(axis=0) / n
+            g0 = ((s - mu) ** 2).sum(axis=0) / n
+            chain_mean.numpy()[:M] = mu
+            chain_g0.numpy()[:M] = g0
+            bad = float(np.sum(~np.isfinite(split(a))))
+            return torch.tensor([mu.sum(), g0.sum(), bad], dtype=torch.float64)
 
     def ess_between_sq(self, chain_mean, centre):
-        return torch.tensor([((chain_mean.numpy() - centre.numpy()[0]) ** 2).sum()], dtype=torch.float64)
+        with np.errstate(invalid="ignore", over="ignore"):
+            return torch.tensor([((chain_mean.numpy() - centre.numpy()[0]) ** 2).sum()], dtype=torch.float64)
 
     def ess_lag_sums(self, x, q, chain_mean, lag0, nlags):
         self._count("ess_lag_sums")
         _, s = self._split(x, q)
         n = s.shape[0]
-        d = s - chain_mean.numpy()
-        return torch.tensor([(d[: n - t] * d[t:]).sum() / n for t in range(lag0, lag0 + nlags)], dtype=torch.float64)
+        d = s - chain_mean.numpy()[:s.shape[1]]
+        with np.errstate(invalid="ignore", over="ignore"):
+            return torch.tensor([(d[: n - t] * d[t:]).sum() / n for t in range(lag0, lag0 + nlags)], dtype=torch.float64)
 
     def ess_acov_sums(self, acor, chain_g0, lag0, nlags):
         self._count("ess_acov_sums")
-        a, g = acor.numpy(), chain_g0.numpy()
-        v = np.where(g != 0.0, a[lag0:lag0 + nlags] * g, 0.0)
-        return torch.from_numpy(v.sum(axis=1))
+        a, g = acor.numpy(), chain_g0.numpy()[:acor.shape[1]]
+        with np.errstate(invalid="ignore"):
+            v = np.where(g != 0.0, a[lag0:lag0 + nlags] * g, 0.0)  # (a chain with gamma_0 = 0 contributes exactly 0)
+        return torch.from_numpy(np.ascontiguousarray(v).sum(axis=1))
 
     def ess_indicator(self, x, q, out):
-        out.numpy()[...] = (x.numpy() <= q).astype(np.float64)
+        with np.errstate(invalid="ignore"):
+            out.numpy()[...] = (x.numpy() <= q).astype(np.float64)
 
     def select_ranks(self, rank, values, targets, out):
+        if not 1 <= targets.numel() <= 8:
+            raise ValueError("bk_select_ranks takes 1 to 8 targets")
         r, v = rank.numpy(), values.numpy()
         for j, t in enumerate(targets.numpy()):
             hit = np.nonzero(r == t)[0]

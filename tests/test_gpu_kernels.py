@@ -731,7 +731,7 @@ def test_long_chains_take_the_fft_formulation(ops):
 @pytest.mark.parametrize("N,C", [(2, 1), (3, 2), (4, 5), (5, 64), (17, 3), (64, 129), (100, 7), (257, 66), (1000, 130),
                                  (4096, 9), (4097, 2), (16384, 5), (40000, 3)])
 def test_autocorr_fft_against_numpy(ops, N, C):
-    """bk_autocorr_fft (Stockham radix-8/4/2 passes across the rows, two real series per complex column, unit-variance
+    """bk_autocorr_fft (Stockham radix-16 passes across the rows, 8 / 4 / 2 for the remainder, two real series per complex column, unit-variance
     scaling on the way in) against autocorr.py:23-33 evaluated with numpy.fft, for every transform size from 4 to
     131,072, odd and even column counts, columns of very different scale side by side, a strided input view."""
     rng = np.random.default_rng(N * 1000 + C)
