@@ -45,6 +45,9 @@ SIGNATURES = {
     "bk_mh_accept": [c_int, P, P, P, P, P, P, P, P, I, P],
     "bk_select_columns": [P, P, P, P, P, P, I, I, I, P],
     "bk_blend_columns": [P, P, P, P, I, I, I, P],
+    "bk_leapfrog_kick_drift_ld": [P, I, P, I, P, I, P, I, P, I, I, P, F, c_int, F, c_int, F, I, I, P],
+    "bk_blend_columns_ld": [P, P, I, P, I, P, I, I, I, P],
+    "bk_select_columns_ld": [P, P, I, P, I, I, I, P],
     "bk_compact_indices": [P, I, P, P, P, P],
     "bk_dr_begin": [P, P, P, P, P, P, I, P],
     "bk_dr_retry_test": [c_int, P, I, P, F, P, I, P],
@@ -355,6 +358,14 @@ class Ops:
                        ptr(grad), grad.stride(0), grad.stride(1), ptr(metric), eps, int(use_pre), pre,
                        int(use_kick), kick, C, D, ptr(n_dev), self._s())
 
+    def kick_drift_ld(self, theta_in, theta_out, rho_in, rho_out, grad, metric, eps, use_pre, pre, use_kick, kick):
+        """kick_drift with each array at its own row pitch (a tile's first step: full-width columns in, tile arrays out)."""
+        D, C = theta_out.shape
+        assert theta_in.shape == (D, C) and rho_in.shape == (D, C) and rho_out.shape == (D, C) and grad.shape == (D, C)
+        self._call("bk_leapfrog_kick_drift_ld", ptr(theta_in), _ld(theta_in), ptr(theta_out), _ld(theta_out), ptr(rho_in),
+                   _ld(rho_in), ptr(rho_out), _ld(rho_out), ptr(grad), grad.stride(0), grad.stride(1), ptr(metric), eps,
+                   int(use_pre), pre, int(use_kick), kick, C, D, self._s())
+
     def first_step_gather(self, theta_in, rho_in, grad_in, src_index, theta_out, rho_out, metric, eps, pre,
                           n_dev=None):
         D, n = theta_out.shape
@@ -428,6 +439,18 @@ class Ops:
         ld = _ld(a)
         assert _ld(b) == ld and _ld(out) == ld
         self._call("bk_blend_columns", ptr(mask), ptr(a), ptr(b), ptr(out), ld, C, D, self._s())
+
+    def blend_columns_ld(self, mask, a, b, out):
+        """blend_columns with each array at its own row pitch (b: a tile's proposal, a / out: columns of the state)."""
+        D, C = out.shape
+        assert a.shape == (D, C) and b.shape == (D, C) and mask.shape[0] == C
+        self._call("bk_blend_columns_ld", ptr(mask), ptr(a), _ld(a), ptr(b), _ld(b), ptr(out), _ld(out), C, D, self._s())
+
+    def select_columns_ld(self, mask, dst, src):
+        """dst <- src on the accepted chains, each array at its own row pitch (src: a tile's gradient)."""
+        D, C = dst.shape
+        assert src.shape == (D, C) and mask.shape[0] == C
+        self._call("bk_select_columns_ld", ptr(mask), ptr(dst), _ld(dst), ptr(src), _ld(src), C, D, self._s())
 
     def compact_indices(self, mask, n, idx_out, count_out, n_dev=None):
         self._call("bk_compact_indices", ptr(mask), n, ptr(idx_out), ptr(count_out), ptr(n_dev), self._s())

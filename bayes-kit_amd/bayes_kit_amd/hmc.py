@@ -133,6 +133,8 @@ class HMCDiag(ManyChainSampler):
         self._logu_bufs = [torch.empty(C, **f64)]
         self._ret = torch.empty(C, **f64)
         self._mask = torch.empty(C, dtype=torch.uint8, device=dev)
+        # tile-major schedule: the momentum of the tile in flight, [D, T] contiguous (allocated here: never inside a capture)
+        self._rho_tile = torch.empty(D * self._chain_tile, **f64) if self._chain_tile < C else None
         self._accepted = torch.zeros(1, dtype=torch.int32, device=dev)
         if self._fused_draw:
             self._part = torch.empty(12 * C, **f64)    # quarter partials of the three per-chain sums
@@ -263,7 +265,7 @@ class HMCDiag(ManyChainSampler):
             self._rng_state.copy_(self._snap[self._pf_slot] if self._snap is not None else self._rng_logical)
             self._pf_ready, self._pf_event = False, None
         self._fused_draw = self._fused = self._fused_zt = False
-        self._rho_bufs = [r if r is not None else torch.empty_like(self._theta_p) for r in self._rho_bufs]
+        self._rho_bufs = [r if r is not None else torch.empty_like(self._thp_raw) for r in self._rho_bufs]
         if self._prefetch and self._snap is not None:
             self._snap, self._rng_logical = None, self._rng_state.clone()
         self._have_cache = False
@@ -297,6 +299,95 @@ class HMCDiag(ManyChainSampler):
         self.placement = {key + "_as_allocated": rep["ms_as_allocated"], key + "_chosen": rep["ms_chosen"],
                           "assignments_tried": rep["assignments_tried"]}
 
+    # -- tile-major scratch ------------------------------------------------------------------------
+    # The tiled model-opaque loop keeps theta' and the trajectory gradient TILE-MAJOR: the block of tile k (chains
+    # [c0, c1), c0 = k*T) is a contiguous [D, c1 - c0] array at element offset D*c0 of the same D*C doubles -- the 63
+    # in-place steps of a tile then walk rows 8*T bytes apart instead of 8*C (profiles/cache_tiles.md, section 6).  Only the
+    # sampler reads those two arrays; whoever else asks (`_theta_p`, `_grad_p`: tests, bench.py --full) gets a [D, C] tensor,
+    # assembled from the blocks when the last draw left them tile-major.
+    _tm_last = False  # the last draw wrote _thp_raw / _gp_raw tile-major
+
+    @staticmethod
+    def tile_major_blocks(C, D, T):
+        """[(c0, c1, offset)]: tile k holds chains [c0, c1) as a contiguous [D, c1 - c0] block `offset` elements into the
+        D*C-element store; every tile but the last has T chains, so offset = D*c0 also when C is ragged."""
+        return [(c0, min(C, c0 + T), D * c0) for c0 in range(0, C, T)]
+
+    def _tm_assemble(self, raw):
+        D, C = self._dim, self._C
+        flat, out = raw.view(-1), torch.empty((D, C), dtype=raw.dtype, device=raw.device)
+        for c0, c1, off in self.tile_major_blocks(C, D, self._chain_tile):
+            out[:, c0:c1].copy_(flat[off:off + D * (c1 - c0)].view(D, c1 - c0))
+        return out
+
+    @property
+    def _theta_p(self):
+        """The proposal of every chain as a [D, C] tensor (the last draw's; a copy while the store is tile-major)."""
+        return self._tm_assemble(self._thp_raw) if self._tm_last else self._thp_raw
+
+    @_theta_p.setter
+    def _theta_p(self, a):
+        self._thp_raw = a
+
+    @property
+    def _grad_p(self):
+        """The gradient at the proposal, as `_theta_p`."""
+        return self._tm_assemble(self._gp_raw) if self._tm_last else self._gp_raw
+
+    @_grad_p.setter
+    def _grad_p(self, a):
+        self._gp_raw = a
+
+    def _tm_flat(self, name):
+        """The D*C doubles behind `name` as a flat tensor (a store with padded rows is replaced by a dense one)."""
+        a = getattr(self, name)
+        if not a.is_contiguous() or a.numel() != self._dim * self._C:
+            a = torch.empty((self._dim, self._C), dtype=a.dtype, device=a.device)
+            setattr(self, name, a)
+        return a.view(-1)
+
+    def _draw_tile_major(self, th, rho, kin0, logu, g, m, eps, half, L):
+        """The L steps, the finish, the accept test, the blend into the new state and the select into the cached gradient,
+        tile by tile: everything a tile's end needs (rho, theta', the proposal's gradient) is still in the cache when it
+        runs.  Values, chains and stream positions are those of the untiled schedule, bit for bit."""
+        ops, D, C, T = self._ops, self._dim, self._C, self._chain_tile
+        thp_f, gp_f = self._tm_flat("_thp_raw"), self._tm_flat("_gp_raw")
+        if self._rho_tile is None or self._rho_tile.numel() != D * T:
+            self._rho_tile = torch.empty(D * T, dtype=torch.float64, device=ops.device)
+        lp0 = self._lp.clone() if self._stat is not None else None  # (warmup: the statistic sees the log density as it was)
+        # the accepted chains take their proposal: a blend into a fresh state array, or (a replayed hipGraph needs fixed
+        # addresses) a select in place -- _take()'s two forms
+        self._out = torch.empty_like(th) if self._rebind else None
+        for c0, c1, off in self.tile_major_blocks(C, D, T):
+            n, sl = c1 - c0, slice(c0, c1)
+            thp_k, gp_k = thp_f[off:off + D * n].view(D, n), gp_f[off:off + D * n].view(D, n)
+            rho_k = self._rho_tile[:D * n].view(D, n)
+            gl = None
+            for s in range(L):
+                if s == 0:  # full-width columns in, the tile's own arrays out
+                    ops.kick_drift_ld(th[:, sl], thp_k, rho[:, sl], rho_k, g[:, sl], m, eps, True, -half, True, eps)
+                else:
+                    ops.kick_drift(thp_k, thp_k, rho_k, rho_k, gl, m, eps, False, 0.0, True, eps)
+                gl = self._eval_grad(thp_k, gp_k, self._lp_p[sl] if s == L - 1 else None)
+            gl = self._materialize(gl, gp_k)
+            # forward half-step + kinetic energy of the proposal [hmc.py:52, :37], accept [hmc.py:60-63], take [hmc.py:61]
+            if self._pd is not None:
+                ops.leapfrog_finish_precond(rho_k, None, gl, self._pd, half, False, self._kin1[sl])
+            else:
+                ops.leapfrog_finish(rho_k, None, gl, m, half, False, self._kin1[sl])
+            ops.mh_accept(_lib.ACCEPT_HMC, self._lp[sl], kin0[sl], self._lp_p[sl], self._kin1[sl], logu[sl],
+                          self._mask[sl], self._ret[sl], self._accepted)
+            if self._rebind:
+                ops.blend_columns_ld(self._mask[sl], th[:, sl], thp_k, self._out[:, sl])
+            else:
+                ops.select_columns_ld(self._mask[sl], th[:, sl], thp_k)
+            ops.select_columns_ld(self._mask[sl], self._grad[:, sl], gp_k)
+        if lp0 is not None:
+            ops.accept_stat(lp0, kin0, self._lp_p, self._kin1, self._stat, self._stat_work)
+        if self._rebind:
+            self._theta_dc = self._out
+        self._tm_last = True
+
     # -- optional cache blocking ----------------------------------------------------------------
     # chain_tile=T runs the L steps tile by tile over blocks of T chains (chains are
     # independent, so this is only a schedule).  The idea: keep a tile's three arrays inside
@@ -317,6 +408,9 @@ class HMCDiag(ManyChainSampler):
     # All of this was measured with the built-in diagonal Gaussian at D = 1,024 and 8,192 to 65,538 chains only: a smaller D
     # (longer rows, the same bytes per tile) and heavier gradient ops follow the same rule unmeasured.
     # An explicit chain_tile wins; chain_tile <= 0 means no tiling.
+    # The tiled loop keeps its scratch tile-major and finishes each tile while it is resident (_draw_tile_major): that took the
+    # 65,536-chain draw from 37.8 to 36.0 ms and 16,384 / 32,768 chains from 9.23 / 18.61 to 9.00 / 18.09; MIN_TILE and the
+    # C >= 2 T rule were not measured again (the new schedule only makes a tile cheaper; the ragged cases above were not rerun).
     LLC_BYTES = 192 << 20
     MIN_TILE = 8192
 
@@ -441,8 +535,8 @@ class HMCDiag(ManyChainSampler):
     def _materialize_dense(self, g):
         if g.dim() == 2 and g.stride(1) == 1:
             return g
-        self._ops.relayout(g, self._grad_p)
-        return self._grad_p
+        self._ops.relayout(g, self._gp_raw)
+        return self._gp_raw
 
     # The side-stream generator (prefetch_rng) runs ONE draw ahead: at the start of draw n the generator
     # of draw n+1 is queued.  `_pf_slot` is the slot the next draw consumes, and the stream position the
@@ -582,8 +676,9 @@ class HMCDiag(ManyChainSampler):
         ops = self._ops
         eps, L, m = float(self._stepsize), int(self._steps), self._metric_dev
         half = 0.5 * eps
-        th, thp = self._theta_dc, self._theta_p
+        th, thp, gp_raw = self._theta_dc, self._thp_raw, self._gp_raw
         mirror = not self._batched
+        self._tm_last = False  # (every path but the tile-major one leaves theta' and its gradient as [D, C] arrays)
 
         # momentum + kinetic energy + accept uniform [hmc.py:56, :37, :60]; the uniform is drawn
         # right after the D normals -- the same stream order as the reference, whose uniform is
@@ -616,9 +711,9 @@ class HMCDiag(ManyChainSampler):
                 self._materialize(self._eval_grad(th, self._grad, self._lp), self._grad)
                 self._have_cache = True
             # [hmc.py:40-53, :59] in one launch; the proposal's gradient is kept for the chains that accept
-            if self._model.bk_hmc_proposal(th, rho, self._grad, thp, self._grad_p, self._lp_p, self._kin1, m, eps, L):
+            if self._model.bk_hmc_proposal(th, rho, self._grad, thp, gp_raw, self._lp_p, self._kin1, m, eps, L):
                 self._accept(kin0, logu)                                                 # [hmc.py:60-63]
-                self._take(th, thp, self._grad, self._grad_p)
+                self._take(th, thp, self._grad, gp_raw)
                 return
 
         if mirror:
@@ -639,10 +734,16 @@ class HMCDiag(ManyChainSampler):
             if not mirror:
                 self._lp_p.copy_(self._lp)
         elif (self._traj_hook and not mirror and self._chain_tile >= self._C
-              and self._model.bk_leapfrog_trajectory(th, rho, g, None, thp, rho, self._grad_p, self._lp_p, m, eps, L,
+              and self._model.bk_leapfrog_trajectory(th, rho, g, None, thp, rho, gp_raw, self._lp_p, m, eps, L,
                                                      hmc_first=True)):
             self._grad_calls += L   # [hmc.py:45-50] in one launch: L gradients of the model's density
-            g_last = self._grad_p
+            g_last = gp_raw
+        elif (self._chain_tile < self._C and not mirror and self._M is None and not self._step_hook
+              and hasattr(ops, "kick_drift_ld")):
+            # the tiled model-opaque loop: tile-major scratch, each tile finished while it is resident (an ops layer without
+            # the per-pitch entry points keeps the loop below on column slices of [D, C] arrays: the same draws)
+            self._draw_tile_major(th, rho, kin0, logu, g, m, eps, half, L)
+            return
         else:
             g_last = None
             T = self._chain_tile
@@ -650,7 +751,7 @@ class HMCDiag(ManyChainSampler):
                 c1 = min(self._C, c0 + T)
                 tile = (c0, c1) != (0, self._C)
                 v = (lambda a: a[:, c0:c1]) if tile else (lambda a: a)
-                th_t, thp_t, rho_t, gp_t, g_t = v(th), v(thp), v(rho), v(self._grad_p), v(g)
+                th_t, thp_t, rho_t, gp_t, g_t = v(th), v(thp), v(rho), v(gp_raw), v(g)
                 lp_t = self._lp_p[c0:c1] if tile else self._lp_p
                 gl = None
                 for n in range(L):
@@ -670,7 +771,7 @@ class HMCDiag(ManyChainSampler):
                     gl = self._eval_grad(thp_t, gp_t, want_lp)
                 if tile:
                     self._materialize(gl, gp_t)
-                    g_last = self._grad_p
+                    g_last = gp_raw
                 else:
                     g_last = gl
         # forward half-step + kinetic energy of the proposal [hmc.py:52, :37]
@@ -687,7 +788,7 @@ class HMCDiag(ManyChainSampler):
         if mirror:
             self._select(self._mask, th, thp)
         else:
-            gp = self._materialize(g_last, self._grad_p) if L > 0 else None
+            gp = self._materialize(g_last, gp_raw) if L > 0 else None
             self._take(th, thp, self._grad if gp is not None else None, gp)
 
     def _accept(self, kin0, logu):

@@ -8,6 +8,7 @@
 // traffic.  The library is compiled with -ffp-contract=off: no FMA, every product and sum
 // is rounded separately, exactly like the NumPy expressions of the reference.
 #include "bk_common.hpp"
+#include "bk_tile_kernels.hpp"
 
 namespace {
 
@@ -701,6 +702,8 @@ __global__ __launch_bounds__(256) void k_precond_pack(const double* v, double* p
   precond[2 * D + d] = 1.0 / x;
 }
 
+constexpr int BK_RED_T_CP = 8, BK_RED_T_U = 8;  // resident-tile finish: chain pairs per wavefront, loads in flight per lane
+
 template <bool KV>
 static int finish_level(const double* rho_in, double* rho_out, int64_t ld, const double* grad, int64_t ldg_d,
                         int64_t ldg_c, const double* metric, double half, int negate, double* kin_out,
@@ -722,7 +725,12 @@ static int finish_level(const double* rho_in, double* rho_out, int64_t ld, const
   const bool vec = plain && C % 2 == 0 && ld % 2 == 0 && C * D >= ((i64)1 << 22) && bk_aligned16(rho_in) &&
                    (!rho_out || bk_aligned16(rho_out)) && (!kin_out || bk_aligned16(kin_out)) &&
                    (!grad || (ldg_c == 1 && ldg_d % 2 == 0 && bk_aligned16(grad)));
-  if (vec)
+  // (a launch whose arrays fit the Infinity Cache -- a tile of the tile-major HMC schedule, 8,192 x 1,024 -- would be 64
+  // workgroups of k_finish_v2: the row-spread form of bk_tile_kernels.hpp, 16 chains per workgroup, the same bits)
+  if (vec && !bk_streams_past_llc(bk_distinct_arrays({rho_in, rho_out, grad}) * C * D))
+    bkt::k_finish_t<BK_RED_T_CP, BK_RED_T_U, 0, KV><<<dim3((unsigned)bk_cdiv(C / 2, BK_RED_T_CP)), dim3(RED_BLOCK), 0, s>>>(
+        rho_in, rho_out, ld, grad, ldg_d, metric, half, negate, kin_out, C / 2, D);
+  else if (vec)
     k_finish_v2<KV><<<dim3((unsigned)bk_cdiv(C / 2, BK_WAVE)), dim3(RED_BLOCK), 0, s>>>(
         rho_in, rho_out, ld, grad, ldg_d, metric, half, negate, kin_out, C / 2, D);
   else
@@ -806,6 +814,88 @@ int bk_blend_columns(const uint8_t* mask, const double* a, const double* b, doub
   } else {
     dim3 grid((unsigned)bk_cdiv(C, 256), (unsigned)bk_cdiv(D, SEL_ROWS));
     k_blend<<<grid, dim3(256), 0, s>>>(mask, a, b, out, ld, C, D);
+  }
+  BK_RETURN_LAUNCH_STATUS();
+}
+
+// ---- one pitch per array: the two ends of a tile of the tile-major HMC schedule (bk_tile_kernels.hpp) ----
+static unsigned ld_rows(i64 n) { return (unsigned)(n < 1 ? 1 : (n > 65535 ? 65535 : n)); }
+
+int bk_leapfrog_kick_drift_ld(const double* theta_in, int64_t ld_ti, double* theta_out, int64_t ld_to,
+                              const double* rho_in, int64_t ld_ri, double* rho_out, int64_t ld_ro, const double* grad,
+                              int64_t ldg_d, int64_t ldg_c, const double* metric, double eps, int use_pre, double pre,
+                              int use_kick, double kick, int64_t C, int64_t D, void* stream) {
+  if (!theta_in || !theta_out || !rho_in || !rho_out || !grad || C < 0 || D < 0) return BK_E_ARG;
+  if (ld_ti < C || ld_to < C || ld_ri < C || ld_ro < C) return BK_E_ALIGN;
+  if ((theta_in == theta_out && ld_ti != ld_to) || (rho_in == rho_out && ld_ri != ld_ro)) return BK_E_ARG;
+  if (C == 0 || D == 0) return BK_OK;
+  hipStream_t s = bk_stream(stream);
+  const bool vec = ldg_c == 1 && C % 2 == 0 && ld_ti % 2 == 0 && ld_to % 2 == 0 && ld_ri % 2 == 0 && ld_ro % 2 == 0 &&
+                   ldg_d % 2 == 0 && bk_aligned16(theta_in) && bk_aligned16(theta_out) && bk_aligned16(rho_in) &&
+                   bk_aligned16(rho_out) && bk_aligned16(grad);
+  if (!vec) {
+    dim3 grid((unsigned)bk_cdiv(C, bkt::KDL_BLOCK), ld_rows(D));
+    bkt::k_kick_drift_ld_s<<<grid, dim3(bkt::KDL_BLOCK), 0, s>>>(theta_in, ld_ti, theta_out, ld_to, rho_in, ld_ri, rho_out,
+                                                                 ld_ro, grad, ldg_d, ldg_c, metric, eps, use_pre, pre,
+                                                                 use_kick, kick, C, D);
+    BK_RETURN_LAUNCH_STATUS();
+  }
+  // The first step of a tile: three full-width inputs stream in (non-temporal: they are not read again before the cache has
+  // turned over), the tile's two outputs are what the next 63 steps work on (plain: they stay).  Outputs that do not fit the
+  // cache either stream out; a launch whose arrays all fit is plain.
+  const bool past = bk_streams_past_llc(bk_distinct_arrays({theta_in, theta_out, rho_in, rho_out, grad}) * C * D);
+  const bool out_past = bk_streams_past_llc(bk_distinct_arrays({theta_out, rho_out}) * C * D);
+  dim3 grid((unsigned)bk_cdiv(C / 2, bkt::KDL_BLOCK), ld_rows(D));
+#define BK_KDL_LAUNCH(H)                                                                                              \
+  bkt::k_kick_drift_ld<H><<<grid, dim3(bkt::KDL_BLOCK), 0, s>>>(theta_in, ld_ti, theta_out, ld_to, rho_in, ld_ri, rho_out, \
+                                                                ld_ro, grad, ldg_d, metric, eps, use_pre, pre, use_kick, \
+                                                                kick, C / 2, D)
+  if (!past) BK_KDL_LAUNCH(0);
+  else if (!out_past) BK_KDL_LAUNCH(bkt::NT_IN);
+  else BK_KDL_LAUNCH(bkt::NT_IN | bkt::NT_OUT);
+#undef BK_KDL_LAUNCH
+  BK_RETURN_LAUNCH_STATUS();
+}
+
+int bk_blend_columns_ld(const uint8_t* mask, const double* a, int64_t ld_a, const double* b, int64_t ld_b, double* out,
+                        int64_t ld_o, int64_t C, int64_t D, void* stream) {
+  if (!mask || !a || !b || !out || C < 0 || D < 0) return BK_E_ARG;
+  if (ld_a < C || ld_b < C || ld_o < C) return BK_E_ALIGN;
+  if (C == 0 || D == 0) return BK_OK;
+  hipStream_t s = bk_stream(stream);
+  if (C % 2 == 0 && ld_a % 2 == 0 && ld_b % 2 == 0 && ld_o % 2 == 0 && bk_aligned16(a) && bk_aligned16(b) &&
+      bk_aligned16(out)) {
+    dim3 grid((unsigned)bk_cdiv(C / 2, 256), ld_rows(bk_cdiv(D, bkt::SELL_ROWS)));
+    // b with the narrower pitch is a tile that the launches before left in the cache: read plainly; a and out are
+    // columns of full-width arrays on their way from and to HBM
+    if (ld_b < ld_a)
+      bkt::k_blend_ld<bkt::NT_IN | bkt::NT_OUT><<<grid, dim3(256), 0, s>>>(mask, a, ld_a, b, ld_b, out, ld_o, C / 2, D);
+    else
+      bkt::k_blend_ld<bkt::NT_IN | bkt::NT_OUT | bkt::NT_TILE><<<grid, dim3(256), 0, s>>>(mask, a, ld_a, b, ld_b, out, ld_o,
+                                                                                        C / 2, D);
+  } else {
+    dim3 grid((unsigned)bk_cdiv(C, 256), ld_rows(D));
+    bkt::k_blend_ld_s<<<grid, dim3(256), 0, s>>>(mask, a, ld_a, b, ld_b, out, ld_o, C, D);
+  }
+  BK_RETURN_LAUNCH_STATUS();
+}
+
+int bk_select_columns_ld(const uint8_t* mask, double* dst, int64_t ld_d, const double* src, int64_t ld_s, int64_t C,
+                         int64_t D, void* stream) {
+  if (!mask || !dst || !src || C < 0 || D < 0) return BK_E_ARG;
+  if (ld_d < C || ld_s < C) return BK_E_ALIGN;
+  if (C == 0 || D == 0) return BK_OK;
+  hipStream_t s = bk_stream(stream);
+  if (C % 2 == 0 && ld_d % 2 == 0 && ld_s % 2 == 0 && bk_aligned16(dst) && bk_aligned16(src)) {
+    dim3 grid((unsigned)bk_cdiv(C / 2, 256), ld_rows(bk_cdiv(D, bkt::SELL_ROWS)));
+    if (ld_s < ld_d)
+      bkt::k_select_ld<bkt::NT_IN | bkt::NT_OUT><<<grid, dim3(256), 0, s>>>(mask, dst, ld_d, src, ld_s, C / 2, D);
+    else
+      bkt::k_select_ld<bkt::NT_IN | bkt::NT_OUT | bkt::NT_TILE><<<grid, dim3(256), 0, s>>>(mask, dst, ld_d, src, ld_s,
+                                                                                         C / 2, D);
+  } else {
+    dim3 grid((unsigned)bk_cdiv(C, 256), ld_rows(D));
+    bkt::k_select_ld_s<<<grid, dim3(256), 0, s>>>(mask, dst, ld_d, src, ld_s, C, D);
   }
   BK_RETURN_LAUNCH_STATUS();
 }

@@ -9,6 +9,7 @@
 // per-chain sum runs sequentially over d in one lane.
 #include "bk_common.hpp"
 #include "bk_elementwise.hpp"
+#include "bk_tile_kernels.hpp"
 #include "bk_mala_step.hpp"
 #include "bk_lanes.hpp"
 
@@ -181,6 +182,8 @@ struct FunnelDensity {
   }
 };
 
+constexpr int BK_RED_T_CP = 8, BK_RED_T_U = 8;  // resident-tile log density: chain pairs per wavefront, loads in flight per lane
+
 int gauss(const double* theta, double* grad, double* logp, i64 ld, const double* lam, i64 C, i64 D,
           const uint32_t* n_dev, void* stream) {
   if (!theta || (!grad && !logp) || C < 0 || D < 0) return BK_E_ARG;
@@ -196,8 +199,14 @@ int gauss(const double* theta, double* grad, double* logp, i64 ld, const double*
     BK_RETURN_LAUNCH_STATUS();
   }
   if (logp) {
-    if (C % 2 == 0 && ld % 2 == 0 && C * D >= ((i64)1 << 22) && bk_aligned16(theta) && bk_aligned16(logp) &&
-        (!grad || bk_aligned16(grad)))
+    const bool vec = C % 2 == 0 && ld % 2 == 0 && C * D >= ((i64)1 << 22) && bk_aligned16(theta) && bk_aligned16(logp) &&
+                     (!grad || bk_aligned16(grad));
+    // (arrays that fit the Infinity Cache -- the last step of a tile of the tile-major HMC schedule, 8,192 x 1,024: 64
+    // workgroups of k_gauss_logp_v2 ran at 1.8 TB/s -- take the row-spread form of bk_tile_kernels.hpp: the same bits)
+    if (vec && !bk_streams_past_llc(bk_distinct_arrays({theta, grad}) * C * D))
+      bkt::k_gauss_logp_t<BK_RED_T_CP, BK_RED_T_U, 0><<<dim3((unsigned)bk_cdiv(C / 2, BK_RED_T_CP)), dim3(RED_BLOCK), 0, s>>>(
+          theta, grad, logp, ld, lam, C / 2, D);
+    else if (vec)
       k_gauss_logp_v2<<<dim3((unsigned)bk_cdiv(C / 2, BK_WAVE)), dim3(RED_BLOCK), 0, s>>>(theta, grad, logp, ld, lam,
                                                                                           C / 2, D);
     else

@@ -250,6 +250,29 @@ int bk_select_columns(const uint8_t* mask, double* dst0, const double* src0,
 int bk_blend_columns(const uint8_t* mask, const double* a, const double* b, double* out,
                      int64_t ld, int64_t C, int64_t D, void* stream);
 
+/* ---- the same three operations with ONE ROW PITCH PER ARRAY (the tile-major HMC schedule) ---------------
+ * A tile of T chains keeps its proposal, momentum and trajectory gradient in contiguous [D][T] arrays that stay
+ * in the Infinity Cache, while the state, the generator's momentum and the cached gradient are columns of [D][C]
+ * arrays.  The launches at a tile's two ends therefore read one kind and write the other:
+ *   bk_leapfrog_kick_drift_ld   the arithmetic of bk_leapfrog_kick_drift, element (d, c) of each array at its own
+ *                               pitch (ld_theta_in, ld_theta_out, ld_rho_in, ld_rho_out); rho_out may be rho_in (then
+ *                               the two pitches are equal), theta_out may be theta_in likewise.  Any strides of grad.
+ *   bk_blend_columns_ld         out[d*ld_out + c] = mask[c] ? b[d*ld_b + c] : a[d*ld_a + c]
+ *   bk_select_columns_ld        dst[d*ld_dst + c] = mask[c] ? src[d*ld_src + c] : dst[d*ld_dst + c]  (one pair)
+ * The same two forms by shape: an even C, even pitches and 16-byte aligned pointers take the 16-byte form (blend and
+ * select rewrite every 16-byte pair: no holes in sectors), anything else the 8-byte form; same results.  Access hints
+ * are chosen per SIDE: a launch whose distinct arrays exceed the cache reads its full-width inputs non-temporally and
+ * writes plainly what fits the cache afterwards (the tile), non-temporally what does not; the tile-resident operand of
+ * blend / select (b, src: the narrower pitch) is read plainly (profiles/cache_tiles.md, section 6). */
+int bk_leapfrog_kick_drift_ld(const double* theta_in, int64_t ld_theta_in, double* theta_out, int64_t ld_theta_out,
+                              const double* rho_in, int64_t ld_rho_in, double* rho_out, int64_t ld_rho_out,
+                              const double* grad, int64_t ldg_d, int64_t ldg_c, const double* metric, double eps,
+                              int use_pre, double pre, int use_kick, double kick, int64_t C, int64_t D, void* stream);
+int bk_blend_columns_ld(const uint8_t* mask, const double* a, int64_t ld_a, const double* b, int64_t ld_b, double* out,
+                        int64_t ld_out, int64_t C, int64_t D, void* stream);
+int bk_select_columns_ld(const uint8_t* mask, double* dst, int64_t ld_dst, const double* src, int64_t ld_src,
+                         int64_t C, int64_t D, void* stream);
+
 /* ---- delayed rejection (DRGHMC) stage helpers -------------------------------------------
  * The reference's recursive accept() with its gradient-cache stack (drghmc.py:82,391-446)
  * is run as a lockstep state machine over lane sets: the chains still inside the stage
