@@ -103,6 +103,8 @@ SIGNATURES = {
     "bk_welford_update_dev": [P, P, I, P, I, P, I, I, I, P],
     "bk_rhat_partials": [P, P, I, I, P, P, I, I, P],
     "bk_accept_stat": [P, P, P, P, I, P, P, P],
+    "bk_chees_sums": [P, I, P, I, P, I, I, P],
+    "bk_chees_stat": [P, I, P, I, P, I, P, P, P, P, P, P, P, I, I, P],
     "bk_chain_mean_var": [P, I, P, I, P, P, I, P],
     "bk_end_pos_pairs": [P, I, I, P, I, P],
     "bk_ess": [P, I, I, c_int, P, P, I, P],
@@ -416,6 +418,28 @@ class Ops:
             work = torch.empty(max(2, 2 * ((C + 255) // 256)), dtype=torch.float64, device=lp_cur.device)
         assert work.numel() >= 2 * ((C + 255) // 256)
         self._call("bk_accept_stat", ptr(lp_cur), ptr(a_cur), ptr(lp_prop), ptr(a_prop), C, ptr(out), ptr(work), self._s())
+
+    def chees_sums(self, theta, theta_p, out):
+        """out[d] = sum_c theta[d][c], out[D + d] = sum_c theta_p[d][c] (out may be longer than 2 D)."""
+        D, C = theta.shape
+        assert tuple(theta_p.shape) == (D, C) and out.is_contiguous() and out.numel() >= 2 * D
+        self._call("bk_chees_sums", ptr(theta), _ld(theta), ptr(theta_p), _ld(theta_p), ptr(out), C, D, self._s())
+
+    @staticmethod
+    def chees_work_elems(C):
+        return max(2, 12 * C + 2 * ((C + 255) // 256))
+
+    def chees_stat(self, theta, theta_p, rho_p, mean, lp_cur, a_cur, lp_prop, a_prop, out, work=None):
+        """out[0] = sum_c w_c g_c, out[1] = chains with w_c > 0 and a non-finite g_c (bk_chees_stat); mean: [2 D], the means
+        of theta and theta_p over all chains; work: chees_work_elems(C) doubles of scratch (allocated here when not given)."""
+        D, C = theta.shape
+        assert tuple(theta_p.shape) == (D, C) and tuple(rho_p.shape) == (D, C)
+        assert mean.is_contiguous() and mean.numel() >= 2 * D and out.is_contiguous() and out.numel() >= 2
+        if work is None:
+            work = torch.empty(self.chees_work_elems(C), dtype=torch.float64, device=theta.device)
+        assert work.numel() >= 12 * C + 2 * ((C + 255) // 256)
+        self._call("bk_chees_stat", ptr(theta), _ld(theta), ptr(theta_p), _ld(theta_p), ptr(rho_p), _ld(rho_p), ptr(mean),
+                   ptr(lp_cur), ptr(a_cur), ptr(lp_prop), ptr(a_prop), ptr(out), ptr(work), C, D, self._s())
 
     def mh_accept(self, mode, lp_cur, a_cur, lp_prop, a_prop, log_u, mask, ret, count):
         self._call("bk_mh_accept", mode, ptr(lp_cur), ptr(a_cur), ptr(lp_prop), ptr(a_prop), ptr(log_u),

@@ -1,7 +1,9 @@
-"""Host side of the cross-chain warmup (HMCDiag.warmup): the window schedule and the dual-averaging controller.
+"""Host side of the cross-chain warmup (HMCDiag.warmup): the window schedule, the dual-averaging controller of the step
+size, and the jitter and the controller of the trajectory length.
 
 Pure Python on a handful of doubles per draw; everything that touches [D, C] arrays stays on the device
-(bk_accept_stat, bk_welford_update, bk_rhat_partials).  The constants are Stan's.
+(bk_accept_stat, bk_welford_update, bk_rhat_partials, bk_chees_sums, bk_chees_stat).  The window schedule's and dual
+averaging's constants are Stan's.
 """
 from __future__ import annotations
 
@@ -56,3 +58,55 @@ class DualAveraging:
     def final(self) -> float:
         """The averaged iterate, exp(xbar): the step size to keep."""
         return math.exp(self.xbar)
+
+
+def radical_inverse2(n: int) -> float:
+    """The base-2 radical inverse of n >= 1 (van der Corput): 1/2, 1/4, 3/4, 1/8, 5/8, ...; exact in a double."""
+    h, f, n = 0.0, 0.5, int(n)
+    while n:
+        if n & 1:
+            h += f
+        n >>= 1
+        f *= 0.5
+    return h
+
+
+def jitter_steps(n: int, T: float, eps: float, max_steps: int) -> int:
+    """Leapfrog steps of jittered draw n = 1, 2, ...: min(max_steps, max(1, ceil(h_n T / eps))), h_n = radical_inverse2(n)."""
+    return int(min(int(max_steps), max(1, math.ceil(radical_inverse2(n) * float(T) / float(eps)))))
+
+
+class TrajectoryAdam:
+    """Gradient ascent on x = log(T) of the ChEES criterion (Hoffman, Radul, Sountsov 2021), the gradient taken across
+    chains (bk_chees_stat): Adam with beta1 = 0, beta2 = 0.95, learning rate 0.025, and DualAveraging's averaging of the
+    iterates (weight k^-0.75).  The constants are this project's choice after the paper."""
+
+    BETA2, RATE, TINY, KAPPA = 0.95, 0.025, 1e-8, 0.75
+
+    def __init__(self, T: float):
+        self.x = math.log(float(T))
+        self.restart()
+
+    def restart(self) -> None:
+        """Keep x, forget the second moment, the update count and the averaged iterate (the geometry has changed)."""
+        self.v = 0.0
+        self.k = 0
+        self.xbar = 0.0
+
+    def step(self, S_wg: float, S_w: float, t: float, eps: float, max_steps: int) -> float:
+        """Feed one draw: S_wg = sum_c w_c g_c and S_w = sum_c w_c over all chains, t = L eps the time that draw integrated;
+        x is kept inside [log eps, log(eps max_steps)].  A draw without weight or with a non-finite sum is skipped.
+        -> the trajectory length of the next draw, exp(x)."""
+        if S_w > 0.0 and math.isfinite(S_wg):
+            g = t * S_wg / S_w
+            self.k += 1
+            self.v = self.BETA2 * self.v + (1.0 - self.BETA2) * g * g
+            self.x += self.RATE * g / (math.sqrt(self.v / (1.0 - self.BETA2 ** self.k)) + self.TINY)
+            self.x = min(max(self.x, math.log(eps)), math.log(eps * max_steps))
+            w = self.k ** (-self.KAPPA)
+            self.xbar = w * self.x + (1.0 - w) * self.xbar
+        return math.exp(self.x)
+
+    def final(self) -> float:
+        """exp of the averaged iterate: the trajectory length to keep (exp(x) when no draw was fed)."""
+        return math.exp(self.xbar if self.k > 0 else self.x)

@@ -45,6 +45,8 @@ class HMCDiag(ManyChainSampler):
         path: str = "auto",
         metric_dense=None,
         precond_diag=None,
+        trajectory_length: Optional[float] = None,
+        max_steps: int = 1024,
         tuning: Optional[dict] = None,
         ops=None,
         **knobs,
@@ -64,7 +66,15 @@ class HMCDiag(ManyChainSampler):
         step while a preconditioner is set: a lane-spread density (bk_hmc_proposal sums the kinetic energy inside its
         launch), and an elementwise from_source / traced density (the whole-draw kernel compiled with it has no
         preconditioned export; it is HBM-bound there instead of register-resident).  ``set_precond_diag`` replaces it between draws,
-        ``warmup`` estimates it."""
+        ``warmup`` estimates it.
+
+        ``trajectory_length`` (extension): an integration TIME T instead of a fixed number of steps, jittered from draw to
+        draw -- jittered draw n = 1, 2, ... takes L_n = min(max_steps, max(1, ceil(h_n T / eps))) leapfrog steps, h_n the
+        base-2 radical inverse of n (1/2, 1/4, 3/4, 1/8, ...) and eps the step size of that draw; ``steps`` is then assigned
+        L_n before every draw.  The jitter consumes no random numbers: stream positions are those of a fixed ``steps``.  A
+        captured draw bakes ``steps`` in, so a graph chosen by default is switched off and an explicit ``graph=True`` is
+        refused.  ``set_trajectory_length`` changes it between draws (None: back to a fixed ``steps``),
+        ``warmup(adapt_trajectory=True)`` learns it."""
         fuse_builtin, fuse_steps = self._resolve_path(path)
         tn = self._resolve_tuning(tuning, knobs)
         chain_tile, graph = tn.get("chain_tile"), tn.get("graph")
@@ -73,6 +83,15 @@ class HMCDiag(ManyChainSampler):
         self._steps = steps
         self._pd = None        # packed preconditioner [3, D] = {v, sqrt(v), 1/v} on the device (precond_diag)
         self._stat = None      # warmup(): where a draw leaves its acceptance statistic (bk_accept_stat)
+        self._chees = None     # warmup(adapt_trajectory=True): the scratch of the trajectory statistic (bk_chees_*)
+        self._T, self._jitter_n, self._last_steps = None, 0, None
+        self._max_steps = self._check_max_steps(max_steps)
+        self._graph_explicit = graph is True
+        if trajectory_length is not None:
+            self._T, self._steps_fixed = self._check_T(trajectory_length), steps
+            if self._graph_explicit:
+                raise ValueError("graph=True cannot be combined with trajectory_length: a captured draw bakes `steps` in")
+            graph = False
         if precond_diag is not None and (metric_diag is not None or metric_dense is not None):
             raise ValueError("give precond_diag or metric_diag / metric_dense, not both")
         self._setup(model, metric_diag, init, seed, chains, chain_id0, ops)
@@ -97,6 +116,7 @@ class HMCDiag(ManyChainSampler):
         if precond_diag is not None:
             self._install_precond(precond_diag)
         self._init_graph(graph, prefetch_rng)
+        self._graph_built = self._use_graph  # (what set_trajectory_length(None) goes back to)
         # built-in separable targets (and separable densities compiled from source) run the whole draw in
         # registers (bk_hmc_draw_gaussian): generator, ONE pass over the state (trajectory + kin0 + kin1 +
         # end-point log density), accept, select; results are bit-identical to the step-by-step path.  With
@@ -275,6 +295,93 @@ class HMCDiag(ManyChainSampler):
     def precond_diag(self):
         """The preconditioner's variances as a host array (None when not set)."""
         return None if self._pd is None else self._pd[0].cpu().numpy().copy()
+
+    # -- a jittered trajectory length ------------------------------------------------------------------
+    @staticmethod
+    def _check_T(T):
+        try:
+            Tf = float(T)
+        except (TypeError, ValueError):
+            raise ValueError(f"trajectory_length must be a finite, positive number, got {T!r}") from None
+        if not (np.isfinite(Tf) and Tf > 0.0):
+            raise ValueError(f"trajectory_length must be a finite, positive number, got {T!r}")
+        return Tf
+
+    @staticmethod
+    def _check_max_steps(n):
+        if isinstance(n, bool) or int(n) != n or int(n) < 1:
+            raise ValueError(f"max_steps must be an integer >= 1, got {n!r}")
+        return int(n)
+
+    def set_trajectory_length(self, T):
+        """Jitter the trajectory around the integration time T from the next draw on (see ``trajectory_length``); None goes
+        back to the fixed ``steps`` it had before.  The jitter counter is kept."""
+        if T is None:
+            if self._T is not None:
+                self._steps = self._steps_fixed
+            self._T = None
+            if self._graph_built and not self._use_graph:
+                self._use_graph = True
+                self._drop_graphs()
+            return
+        T = self._check_T(T)
+        if self._use_graph:
+            if self._graph_explicit:
+                raise ValueError("graph=True cannot be combined with trajectory_length: a captured draw bakes `steps` in")
+            self._use_graph = False  # (a graph chosen by default; the eager launches keep its in-place select)
+            self._drop_graphs()
+        if self._T is None:
+            self._steps_fixed = self._steps
+        self._T = T
+
+    @property
+    def trajectory_length(self):
+        """The integration time the draws are jittered around (None: a fixed ``steps``)."""
+        return self._T
+
+    @property
+    def max_steps(self):
+        return self._max_steps
+
+    @property
+    def last_steps(self):
+        """Leapfrog steps of the most recent draw (None before the first)."""
+        return self._last_steps
+
+    def _next_steps(self):
+        """Assign ``steps`` for the draw about to run: L_n of the next jittered draw, or what it is."""
+        if self._T is not None:
+            from .adapt import jitter_steps
+
+            self._jitter_n += 1
+            self._steps = jitter_steps(self._jitter_n, self._T, float(self._stepsize), self._max_steps)
+        self._last_steps = int(self._steps)
+
+    def _enter_whole_draw(self):
+        """The mirror of _leave_whole_draw, between two draws: the stream goes back to the logical position (a momentum
+        generated ahead in the state layout is dropped), the chain-major normals and the stream snapshots come back, graphs
+        are dropped.  The whole-draw kernel needs the current log density only, which the step-by-step path kept."""
+        if self._prefetch and self._pf_ready:
+            if self._pf_event is not None:
+                torch.cuda.current_stream().wait_event(self._pf_event)
+            self._rng_state.copy_(self._rng_logical if self._snap is None else self._snap[self._pf_slot])
+            self._pf_ready, self._pf_event = False, None
+        D, C, dev = self._dim, self._C, self._ops.device
+        self._fused_draw = self._fused = True
+        self._fused_zt = self._rng_kind == _lib.RNG_PHILOX and D >= 32
+        n_slots = 2 if self._prefetch else 1
+        if getattr(self, "_part", None) is None:
+            self._part = torch.empty(12 * C, dtype=torch.float64, device=dev)
+        if self._fused_zt:
+            zt = list(getattr(self, "_zt_bufs", []))
+            while len(zt) < n_slots:
+                zt.append(torch.empty((C, (D + 7) // 8 * 8), dtype=torch.float64, device=dev))
+            self._zt_bufs = zt
+            self._rho_bufs = [None] * n_slots  # (the momentum never exists in the state layout)
+            if self._prefetch:
+                self._snap = [torch.empty_like(self._rng_state) for _ in range(2)]
+        self._pf_kin_stale = False
+        self._drop_graphs()
 
     def _tune_placement(self):
         """Roles (theta', grad', rho of each slot, grad): see ManyChainSampler._tune_roles."""
@@ -472,12 +579,17 @@ class HMCDiag(ManyChainSampler):
         super().load_state_dict(sd)
 
     def _state_extra(self):
-        return {"stepsize": float(self._stepsize), "precond_diag": None if self._pd is None else self._pd[0].cpu().clone()}
+        return {"stepsize": float(self._stepsize), "precond_diag": None if self._pd is None else self._pd[0].cpu().clone(),
+                "trajectory_length": self._T, "max_steps": self._max_steps, "jitter_n": self._jitter_n}
 
     def _load_extra(self, extra):
         # (checkpoints written before the step size and the preconditioner were carried hold neither: nothing changes)
         if "stepsize" in extra:
             self._stepsize = extra["stepsize"]
+        if "trajectory_length" in extra:  # (older checkpoints: the sampler keeps what it was built with)
+            self._max_steps = self._check_max_steps(extra["max_steps"])
+            self.set_trajectory_length(extra["trajectory_length"])
+            self._jitter_n = int(extra["jitter_n"])
         pv = extra.get("precond_diag")
         if pv is not None:
             # (randomness generated ahead was dropped by load_state_dict: nothing here moves the restored stream)
@@ -586,7 +698,7 @@ class HMCDiag(ManyChainSampler):
         return (float(self._stepsize), int(self._steps))
 
     # -- warmup -------------------------------------------------------------------------------------
-    def warmup(self, draws, target_accept=0.8, adapt_metric=True, group=None):
+    def warmup(self, draws, target_accept=0.8, adapt_metric=True, group=None, *, adapt_trajectory=False, max_steps=None):
         """Run `draws` draws that tune the step size and (adapt_metric) the diagonal preconditioner from ALL chains of all
         ranks, then keep the tuned values: afterwards the sampler samples with them.  -> report dict: ``stepsize``,
         ``precond_diag`` (host copy, None if none is set), per-draw ``eps`` and ``alpha`` histories, ``window_ends``,
@@ -597,7 +709,22 @@ class HMCDiag(ManyChainSampler):
         (bk_accept_stat; a NaN difference counts 0).  Metric: Welford moments of the state after every draw inside a window
         of adapt.warmup_windows; at a window's end v = N/(N+5) * pooled variance + 1e-3 * 5/(N+5), N = draws in the window
         x chains, becomes the preconditioner (set_precond_diag), the moments are reset and the step size restarts from
-        its averaged iterate.  `steps` is not adapted.
+        its averaged iterate.
+
+        Trajectory length (adapt_trajectory=True; `steps` is not adapted otherwise): ChEES-HMC (Hoffman, Radul, Sountsov
+        2021).  Every warmup draw is jittered around the integration time T (see ``trajectory_length``; it starts from the
+        sampler's, or steps * stepsize), and adapt.TrajectoryAdam ascends log T along the gradient of
+        1/4 E[(|theta' - E theta'|^2 - |theta - E theta|^2)^2] taken across all chains of all ranks
+        (bk_chees_sums, bk_chees_stat: one more pair of passes over the state, the proposal and its velocity per draw; its
+        two outputs travel in the same vector and the same host read as the acceptance statistic).  At a metric window's
+        end the controller restarts from its current T.  Afterwards ``trajectory_length`` stays set to the averaged iterate,
+        so sample() keeps jittering (and replays no captured graph).  The statistic needs the proposal's velocity in memory:
+        for the duration of the warmup the whole-draw kernel is left for the step-by-step path (and entered again
+        afterwards), the lane-spread one-launch trajectory and the tile-major schedule are not taken -- all of them give the
+        same draws bit for bit, so the report does not depend on the path.  Needs a batched model and refuses metric_dense
+        (the dense velocity is not what the kick and drift kernels hold); ``max_steps`` replaces the sampler's bound.  The
+        report gains ``trajectory_length``, per-draw ``T`` and ``steps`` and ``nonfinite_chains`` (chains with weight whose
+        gradient term was not finite, left out of the sum).
 
         Cost: the statistic kernel, ONE host read of three doubles (summed over ranks in rank order, dist.gather_sum) and,
         inside windows, a Welford update per draw; two more [D, C] arrays for the window moments, freed at the end.  The
@@ -611,7 +738,7 @@ class HMCDiag(ManyChainSampler):
         contraction (after a restart it swings the step size across the stability limit and back), so that rounding grows: two
         world sizes end at different, equally valid adaptations (observed: eps 0.647 against 0.675, v within 3 % of each
         other and of the truth)."""
-        from .adapt import DualAveraging, warmup_windows
+        from .adapt import DualAveraging, TrajectoryAdam, warmup_windows
         from .diagnostics import RunningMoments, _gather_sum, pooled_variance_from_moments
 
         draws = int(draws)
@@ -622,6 +749,19 @@ class HMCDiag(ManyChainSampler):
         if adapt_metric and (self._M is not None or (self._pd is None and self._metric_dev is not None)):
             raise ValueError("warmup: adapt_metric=True estimates precond_diag, which cannot be combined with "
                              "metric_diag / metric_dense (pass adapt_metric=False to tune the step size alone)")
+        if adapt_trajectory:
+            if not self._batched:
+                raise ValueError("warmup: adapt_trajectory=True needs a batched device model (the gradient is taken across "
+                                 "chains)")
+            if self._M is not None:
+                raise ValueError("warmup: adapt_trajectory=True cannot be combined with metric_dense (the dense velocity is "
+                                 "not what the kick and drift kernels hold)")
+            if self._graph_explicit:
+                raise ValueError("warmup: adapt_trajectory=True jitters every draw, which graph=True cannot replay")
+            if max_steps is not None:
+                max_steps = self._check_max_steps(max_steps)
+        elif max_steps is not None:
+            raise ValueError("warmup: max_steps bounds the adapted trajectory, pass it with adapt_trajectory=True")
         if not self._batched:
             raise ValueError("warmup needs a batched device model (the statistics are taken across chains)")
         ops, dev, C, D = self._ops, self._ops.device, self._C, self._dim
@@ -630,13 +770,30 @@ class HMCDiag(ManyChainSampler):
             ends = []
         da = DualAveraging(float(self._stepsize), float(target_accept))
         mom = RunningMoments(D, C, ops) if ends else None
-        self._stat = torch.zeros(3, dtype=torch.float64, device=dev)  # {sum of the statistic, NaN chains, chains}
+        # {sum of the statistic, NaN chains, chains} and, adapting the trajectory, {sum of w g, chains with a non-finite g}
+        self._stat = torch.zeros(5 if adapt_trajectory else 3, dtype=torch.float64, device=dev)
         self._stat[2] = float(C)
         self._stat_work = torch.empty(max(2, 2 * ((C + 255) // 256)), dtype=torch.float64, device=dev)
         eps_hist, alpha_hist, nan_chains = [], [], 0
+        ta, was_fused, T_hist, steps_hist, nonfinite = None, False, [], [], 0
+        if adapt_trajectory:
+            if max_steps is not None:
+                self._max_steps = max_steps
+            self.set_trajectory_length(self._T if self._T is not None else float(self._steps) * float(self._stepsize))
+            ta = TrajectoryAdam(self._T)
+            was_fused = self._fused_draw
+            if was_fused:
+                self._leave_whole_draw()
+            sums = torch.zeros(2 * D + 1, dtype=torch.float64, device=dev)  # {sum theta, sum theta', chains}
+            sums[2 * D] = float(C)
+            self._chees = (sums, torch.empty(ops.chees_work_elems(C), dtype=torch.float64, device=dev), group)
         try:
             for it in range(draws):
                 eps_hist.append(float(self._stepsize))
+                self._next_steps()
+                if ta is not None:
+                    T_hist.append(float(self._T))
+                    steps_hist.append(int(self._steps))
                 self._draw()
                 self._join_side_stream()
                 self._draws += 1
@@ -648,6 +805,14 @@ class HMCDiag(ManyChainSampler):
                 if mom is not None and init <= it < draws - term:
                     mom.update(self._theta_dc, layout="dc")
                 eps = da.step(alpha)
+                if ta is not None:
+                    nonfinite += int(tot[4])
+                    self._T = ta.step(float(tot[3]), float(tot[0]), self._steps * eps_hist[-1], eps_hist[-1],
+                                      self._max_steps)
+                    if it + 1 in ends:
+                        ta.restart()  # (the geometry changes with the metric below)
+                    if it + 1 == draws:
+                        self._T = ta.final()
                 if it + 1 in ends:
                     n_eff = float(mom.n) * chains_total
                     var = pooled_variance_from_moments(mom.mean, mom.m2, mom.n, ops, group)
@@ -659,14 +824,20 @@ class HMCDiag(ManyChainSampler):
                     eps = da.final()
                 self._stepsize = eps
         finally:
-            self._stat, self._stat_work = None, None
+            self._stat, self._stat_work, self._chees, self._rho_cur = None, None, None, None
             del mom
             self._drop_graphs()
-        return {"stepsize": float(self._stepsize), "precond_diag": self.precond_diag, "eps": eps_hist, "alpha": alpha_hist,
-                "window_ends": list(ends), "nan_chains": nan_chains}
+            if was_fused and (self._pd is None or hasattr(self._model, "bk_hmc_draw_precond")):
+                self._enter_whole_draw()
+        rep = {"stepsize": float(self._stepsize), "precond_diag": self.precond_diag, "eps": eps_hist, "alpha": alpha_hist,
+               "window_ends": list(ends), "nan_chains": nan_chains}
+        if ta is not None:
+            rep.update(trajectory_length=float(self._T), T=T_hist, steps=steps_hist, nonfinite_chains=nonfinite)
+        return rep
 
     # -- one draw for every chain ------------------------------------------------------------------
     def sample(self):
+        self._next_steps()
         self._run_draw(self._draw)
         self._join_side_stream()
         self._draws += 1
@@ -685,6 +856,10 @@ class HMCDiag(ManyChainSampler):
         # the next value of the stream whatever happens in between
         rho, kin0, logu = self._current_randomness()
         self._start_next_randomness()  # hides under this draw's launches
+        # warmup(adapt_trajectory=True): the trajectory statistic reads the proposal's velocity, so the finish launch stores
+        # it (in place) and the paths that keep it on chip or in a tile's scratch are not taken
+        chees = self._chees is not None
+        self._rho_cur = rho if chees else None
 
         if self._fused_draw:
             if not self._have_cache:
@@ -706,7 +881,7 @@ class HMCDiag(ManyChainSampler):
             self._take(th, thp)
             return
 
-        if self._lanes_traj and L >= 1 and self._pd is None:
+        if self._lanes_traj and L >= 1 and self._pd is None and not chees:
             if not self._have_cache:
                 self._materialize(self._eval_grad(th, self._grad, self._lp), self._grad)
                 self._have_cache = True
@@ -739,7 +914,7 @@ class HMCDiag(ManyChainSampler):
             self._grad_calls += L   # [hmc.py:45-50] in one launch: L gradients of the model's density
             g_last = gp_raw
         elif (self._chain_tile < self._C and not mirror and self._M is None and not self._step_hook
-              and hasattr(ops, "kick_drift_ld")):
+              and hasattr(ops, "kick_drift_ld") and not chees):
             # the tiled model-opaque loop: tile-major scratch, each tile finished while it is resident (an ops layer without
             # the per-pitch entry points keeps the loop below on column slices of [D, C] arrays: the same draws)
             self._draw_tile_major(th, rho, kin0, logu, g, m, eps, half, L)
@@ -776,9 +951,9 @@ class HMCDiag(ManyChainSampler):
                     g_last = gl
         # forward half-step + kinetic energy of the proposal [hmc.py:52, :37]
         if self._pd is not None:
-            ops.leapfrog_finish_precond(rho, None, g_last, self._pd, half, False, self._kin1)
+            ops.leapfrog_finish_precond(rho, rho if chees else None, g_last, self._pd, half, False, self._kin1)
         elif self._M is None:
-            ops.leapfrog_finish(rho, None, g_last, m, half, False, self._kin1)
+            ops.leapfrog_finish(rho, rho if chees else None, g_last, m, half, False, self._kin1)
         else:
             ops.leapfrog_finish(rho, rho, self._mg(g_last), None, half, False, None)
             self._dense_kinetic(rho, self._kin1, self._mv)
@@ -796,8 +971,24 @@ class HMCDiag(ManyChainSampler):
         (bk_accept_stat, before the test overwrites the current log density)."""
         if self._stat is not None:
             self._ops.accept_stat(self._lp, kin0, self._lp_p, self._kin1, self._stat, self._stat_work)
+        if self._chees is not None:
+            self._chees_launch(kin0)
         self._ops.mh_accept(_lib.ACCEPT_HMC, self._lp, kin0, self._lp_p, self._kin1, logu,
                             self._mask, self._ret, self._accepted)
+
+    def _chees_launch(self, kin0):
+        """The trajectory statistic of this draw into _stat[3:5] (state, log density and proposal are still intact): sums
+        over this rank's chains, all ranks' sums in rank order, the means (divided by the chain count as a TENSOR: the same
+        doubles on every device, see diagnostics._cross_chain_moments), then the weighted gradient."""
+        from .diagnostics import _gather_sum
+
+        ops, D = self._ops, self._dim
+        sums, work, group = self._chees
+        ops.chees_sums(self._theta_dc, self._thp_raw, sums)
+        tot = _gather_sum(sums, group)
+        mean = (tot[0:2 * D] / tot[2 * D:2 * D + 1]).contiguous()
+        ops.chees_stat(self._theta_dc, self._thp_raw, self._rho_cur, mean, self._lp, kin0, self._lp_p, self._kin1,
+                       self._stat[3:5], work)
 
     def _take(self, th, thp, g=None, gp=None):
         """The accepted chains take their proposal [hmc.py:61] (and its cached gradient)."""

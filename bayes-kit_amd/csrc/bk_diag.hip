@@ -509,6 +509,112 @@ __global__ __launch_bounds__(256) void k_accept_stat_combine(const double* work,
   }
 }
 
+// ---- the cross-chain statistic a trajectory-length adaptation ascends (bk_chees_sums, bk_chees_stat) ----------------
+// Sums over chains of the state and of the proposal, one workgroup per dimension, in k_rhat_partials' order (thread t adds
+// chains t, t + 256, .. in order, the 256 sums are halved 128 .. 1): out[d] and out[D + d].
+__global__ __launch_bounds__(256) void k_chees_sums(const double* theta, i64 ld, const double* theta_p, i64 ldp,
+                                                    double* out, i64 C, i64 D) {
+  __shared__ double red[2][256];
+  const i64 d = blockIdx.x;
+  const double* a = theta + d * ld;
+  const double* b = theta_p + d * ldp;
+  double s0 = 0.0, s1 = 0.0;
+  for (i64 c = threadIdx.x; c < C; c += 256) {
+    s0 = s0 + a[c];
+    s1 = s1 + b[c];
+  }
+  red[0][threadIdx.x] = s0;
+  red[1][threadIdx.x] = s1;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) {
+      red[0][threadIdx.x] += red[0][threadIdx.x + w];
+      red[1][threadIdx.x] += red[1][threadIdx.x + w];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    out[d] = red[0][0];
+    out[D + d] = red[1][0];
+  }
+}
+
+// Quarter blockIdx.y of the three per-chain sums A = sum dp*dp, B = sum dc*dc, P = sum dp*rho' (dp = theta' - mean',
+// dc = theta - mean), lane = chain, sequential in d inside the quarter [q*Dq, (q+1)*Dq), Dq = ceil(D/4) -- the library's
+// quarter order, spread over four workgroups so that few chains of many dimensions still fill the chip.  Eight rows of
+// loads are in flight per lane; the additions stay in order.  part: [4][3][C].
+constexpr int CH_UNROLL = 8;
+__global__ __launch_bounds__(256) void k_chees_quarters(const double* theta, i64 ld, const double* theta_p, i64 ldp,
+                                                        const double* rho_p, i64 ldr, const double* mean, double* part,
+                                                        i64 C, i64 D) {
+  const i64 c = (i64)blockIdx.x * 256 + threadIdx.x;
+  if (c >= C) return;
+  const int q = blockIdx.y;
+  const i64 Dq = (D + 3) / 4;
+  const i64 dlo = q * Dq, dhi = (dlo + Dq < D) ? dlo + Dq : D;
+  double A = 0.0, B = 0.0, P = 0.0;
+  for (i64 d0 = dlo; d0 < dhi; d0 += CH_UNROLL) {
+    double t[CH_UNROLL], tp[CH_UNROLL], r[CH_UNROLL];
+#pragma unroll
+    for (int u = 0; u < CH_UNROLL; ++u)
+      if (d0 + u < dhi) {
+        t[u] = theta[(d0 + u) * ld + c];
+        tp[u] = theta_p[(d0 + u) * ldp + c];
+        r[u] = rho_p[(d0 + u) * ldr + c];
+      }
+#pragma unroll
+    for (int u = 0; u < CH_UNROLL; ++u)
+      if (d0 + u < dhi) {
+        const double dp = tp[u] - mean[D + d0 + u], dc = t[u] - mean[d0 + u];
+        A = A + dp * dp;
+        B = B + dc * dc;
+        P = P + dp * r[u];
+      }
+  }
+  part[(i64)(q * 3 + 0) * C + c] = A;
+  part[(i64)(q * 3 + 1) * C + c] = B;
+  part[(i64)(q * 3 + 2) * C + c] = P;
+}
+
+// g_c = (A - B) * P from the quarters as ((p0 + p1) + p2) + p3, weighted by k_accept_stat_partials' statistic of the same
+// energies; the sums over chains are that kernel's tree (work[b]: sum of w*g, work[nb + b]: chains with w > 0 whose g is
+// not finite), finished by k_accept_stat_combine.
+__global__ __launch_bounds__(256) void k_chees_partials(const double* part, const double* lp_cur, const double* a_cur,
+                                                        const double* lp_prop, const double* a_prop, i64 C,
+                                                        double* work, i64 nb) {
+  __shared__ double ps[4], pn[4];
+  const i64 c = (i64)blockIdx.x * 256 + threadIdx.x;
+  double s = 0.0, nn = 0.0;
+  if (c < C) {
+    const double a0 = a_cur ? a_cur[c] : 0.0, a1 = a_prop ? a_prop[c] : 0.0;
+    const double h0 = lp_cur[c] - a0, h1 = lp_prop[c] - a1;
+    const double d = h1 - h0;
+    const double w = (d != d) ? 0.0 : fmin(1.0, bk_exp(fmin(0.0, d)));
+    if (w > 0.0) {
+      double q[3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k)
+        q[k] = ((part[(i64)(0 + k) * C + c] + part[(i64)(3 + k) * C + c]) + part[(i64)(6 + k) * C + c]) +
+               part[(i64)(9 + k) * C + c];
+      const double g = (q[0] - q[1]) * q[2];
+      if (isfinite(g)) s = w * g;
+      else nn = 1.0;
+    }
+  }
+  s = wave_sum(s);
+  nn = wave_sum(nn);
+  const int wv = bk_wave_id();
+  if ((threadIdx.x & (BK_WAVE - 1)) == 0) {
+    ps[wv] = s;
+    pn[wv] = nn;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    work[blockIdx.x] = ((ps[0] + ps[1]) + ps[2]) + ps[3];
+    work[nb + blockIdx.x] = ((pn[0] + pn[1]) + pn[2]) + pn[3];
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -562,6 +668,32 @@ int bk_accept_stat(const double* lp_cur, const double* a_cur, const double* lp_p
   if (nb > 0)
     k_accept_stat_partials<<<dim3((unsigned)nb), dim3(256), 0, s>>>(lp_cur, a_cur, lp_prop, a_prop, C, work, nb);
   k_accept_stat_combine<<<dim3(1), dim3(256), 0, s>>>(work, nb, out);  // (C == 0: out = {0, 0})
+  BK_RETURN_LAUNCH_STATUS();
+}
+
+int bk_chees_sums(const double* theta, int64_t ld, const double* theta_p, int64_t ldp, double* out, int64_t C, int64_t D,
+                  void* stream) {
+  if (!theta || !theta_p || !out || C < 0 || D < 0) return BK_E_ARG;
+  if (ld < C || ldp < C) return BK_E_ALIGN;
+  if (D == 0) return BK_OK;
+  k_chees_sums<<<dim3((unsigned)D), dim3(256), 0, bk_stream(stream)>>>(theta, ld, theta_p, ldp, out, C, D);
+  BK_RETURN_LAUNCH_STATUS();
+}
+
+int bk_chees_stat(const double* theta, int64_t ld, const double* theta_p, int64_t ldp, const double* rho_p, int64_t ldr,
+                  const double* mean, const double* lp_cur, const double* a_cur, const double* lp_prop,
+                  const double* a_prop, double* out, double* work, int64_t C, int64_t D, void* stream) {
+  if (!out || C < 0 || D < 0) return BK_E_ARG;
+  if (C > 0 && (!theta || !theta_p || !rho_p || !mean || !lp_cur || !lp_prop || !work)) return BK_E_ARG;
+  if (ld < C || ldp < C || ldr < C) return BK_E_ALIGN;
+  const i64 nb = bk_cdiv(C, 256);
+  hipStream_t s = bk_stream(stream);
+  double* tree = work + 12 * C;
+  if (nb > 0) {
+    k_chees_quarters<<<dim3((unsigned)nb, 4), dim3(256), 0, s>>>(theta, ld, theta_p, ldp, rho_p, ldr, mean, work, C, D);
+    k_chees_partials<<<dim3((unsigned)nb), dim3(256), 0, s>>>(work, lp_cur, a_cur, lp_prop, a_prop, C, tree, nb);
+  }
+  k_accept_stat_combine<<<dim3(1), dim3(256), 0, s>>>(tree, nb, out);  // (C == 0: out = {0, 0})
   BK_RETURN_LAUNCH_STATUS();
 }
 

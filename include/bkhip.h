@@ -836,6 +836,29 @@ int bk_rhat_partials(const double* mean, const double* m2, int64_t ld, int64_t n
 int bk_accept_stat(const double* lp_cur, const double* a_cur, const double* lp_prop, const double* a_prop, int64_t C,
                    double* out, double* work, void* stream);
 
+/* The cross-chain statistic a trajectory-length adaptation ascends (ChEES: Hoffman, Radul, Sountsov 2021), in two
+ * launches around the caller's division by the chain count.  theta / theta_p: state and proposal [D][ld / ldp], rho_p: the
+ * proposal's velocity [D][ldr], all before the accept test.
+ *
+ * bk_chees_sums: out[d] = sum_c theta[d][c], out[D + d] = sum_c theta_p[d][c], in bk_rhat_partials' order (one workgroup
+ * per d: thread t adds chains t, t+256, .. in order, the 256 sums are halved 128, 64, .. 1).
+ *
+ * bk_chees_stat: mean[0..D) / mean[D..2D) are the means of theta / theta_p over ALL chains (of all ranks).  Per chain
+ *     dp = theta_p[d][c] - mean[D + d]     dc = theta[d][c] - mean[d]
+ *     A = sum_d dp*dp     B = sum_d dc*dc     P = sum_d dp*rho_p[d][c]          g_c = (A - B) * P
+ *     w_c = 0 if d_c is NaN, else min(1, bk_exp(min(0, d_c)))                     d_c as in bk_accept_stat
+ *     out[0] = sum_c w_c*g_c   over the chains with w_c > 0 and g_c finite
+ *     out[1] = number of chains with w_c > 0 and g_c not finite
+ * The per-chain sums run over four contiguous quarters of d (ceil(D/4) each), sequential inside a quarter, combined
+ * ((p0+p1)+p2)+p3, every product and sum rounded on its own; the sums over chains are bk_accept_stat's tree.  No
+ * floating-point atomics: the bits depend on (C, D) only.  a_cur / a_prop NULL = zeros.
+ * work: caller scratch of 12*C + 2*ceil(C/256) doubles.  C = 0: out = {0, 0}. */
+int bk_chees_sums(const double* theta, int64_t ld, const double* theta_p, int64_t ldp, double* out, int64_t C, int64_t D,
+                  void* stream);
+int bk_chees_stat(const double* theta, int64_t ld, const double* theta_p, int64_t ldp, const double* rho_p, int64_t ldr,
+                  const double* mean, const double* lp_cur, const double* a_cur, const double* lp_prop,
+                  const double* a_prop, double* out, double* work, int64_t C, int64_t D, void* stream);
+
 /* Per-chain mean and ddof=1 variance of a stored series x[t*ld + c], t < len[c] (len NULL =
  * all N): the two list comprehensions of rhat.py:165-166 for ragged chains. */
 int bk_chain_mean_var(const double* x, int64_t ld, const int32_t* len, int64_t N,
