@@ -21,11 +21,23 @@ constexpr int TG_BLOCK = 256;
 // grad = -(lam*theta)  (lam NULL -> grad = -theta), two chains per lane
 typedef double dvec2 __attribute__((ext_vector_type(2)));
 
+// Row sweep of the gradient-only kernels.  The integrator's launches (bk_integrator.hip) put the row in blockIdx.y and
+// sweep it ascending; a gradient op between two of them that sweeps DESCENDING starts with the rows its producer touched
+// last and ends with the rows its consumer reads first, which are then still in the XCDs' L2s: 66.5 -> 64.5 us per
+// in-place step of an 8,192 x 1,024 tile (profiles/cache_tiles.md section 7).  That pays only where a column block meets
+// the same L2 in both launches.  Workgroups are dealt round-robin over the 8 XCDs in launch order, so it does when
+// gridDim.x is a multiple of 8; with gridDim.x = 4 (2,048 chains) the reversed sweep reads its producer's rows out of
+// another XCD's L2 and the step is 2.7 us of 18 SLOWER, so every other grid keeps the ascending sweep.  Placement is
+// observed behaviour, not a contract: this is a speed hint, the kernels are elementwise and no bit depends on it.
+__device__ __forceinline__ i64 tg_row_group() {
+  return gridDim.x % 8 == 0 ? (i64)gridDim.y - 1 - blockIdx.y : (i64)blockIdx.y;
+}
+
 template <int ROWS, bool NT>
 __global__ __launch_bounds__(TG_BLOCK) void k_gauss_grad_v2(const double* th, double* g, i64 ld,
                                                             const double* lam, i64 C2, i64 D) {
   i64 c2 = (i64)blockIdx.x * TG_BLOCK + threadIdx.x;
-  i64 d0 = (i64)blockIdx.y * ROWS;
+  i64 d0 = tg_row_group() * ROWS;
   if (c2 >= C2) return;
   dvec2 t[ROWS];
   double l[ROWS];
@@ -53,7 +65,7 @@ __global__ __launch_bounds__(TG_BLOCK) void k_gauss_grad_s(const double* th, dou
                                                            const uint32_t* n_dev) {
   const i64 C = bk_lanes(C_host, n_dev);
   i64 c = (i64)blockIdx.x * TG_BLOCK + threadIdx.x;
-  i64 d0 = (i64)blockIdx.y * TG_ROWS;
+  i64 d0 = tg_row_group() * TG_ROWS;
   if (c >= C) return;
 #pragma unroll
   for (int i = 0; i < TG_ROWS; ++i)

@@ -5,6 +5,9 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off tools/cache_tile_bench.hip -o cache_tile_bench
 //   cache_tile_bench C D ld              every pair (a tile of a 65,536-chain state: 8192 1024 65536)
 //   cache_tile_bench C D ld KD G         one pair, e.g. under rocprofv3 --kernel-trace --stats
+//   cache_tile_bench C D ld order        the library's plain pair with each kernel's rows swept ascending or descending: the
+//                                        four combinations, then the first again (profiles/cache_tiles.md section 7)
+//   cache_tile_bench C D ld order KD G   one of them (0 ascending, 1 descending), e.g. under rocprofv3 --pmc FETCH_SIZE
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -85,18 +88,20 @@ __device__ __forceinline__ void kd_unit(i64 c2, i64 d0, const double* th_in, dou
 }
 
 // PERSIST: grid of gridDim.x workgroups walks the (chain block, row group) units in launch order
-template <int ROWS, int NT, int BLOCK, bool PERSIST>
+// DESC: the row groups from the last to the first in launch order (the block-to-row map only)
+template <int ROWS, int NT, int BLOCK, bool PERSIST, bool DESC = false>
 __global__ __launch_bounds__(BLOCK) void k_kd(const double* th_in, double* th_out, const double* rho_in, double* rho_out,
                                               i64 ld, const double* grad, i64 ldg, const double* metric, double eps,
                                               int use_pre, double pre, int use_kick, double kick, i64 C2, i64 D) {
   if (PERSIST) {
     const i64 nx = (C2 + BLOCK - 1) / BLOCK, ny = (D + ROWS - 1) / ROWS;
     for (i64 u = blockIdx.x; u < nx * ny; u += gridDim.x)
-      kd_unit<ROWS, NT>((u % nx) * BLOCK + threadIdx.x, (u / nx) * ROWS, th_in, th_out, rho_in, rho_out, ld, grad, ldg,
-                        metric, eps, use_pre, pre, use_kick, kick, C2, D);
+      kd_unit<ROWS, NT>((u % nx) * BLOCK + threadIdx.x, (DESC ? ny - 1 - u / nx : u / nx) * ROWS, th_in, th_out, rho_in,
+                        rho_out, ld, grad, ldg, metric, eps, use_pre, pre, use_kick, kick, C2, D);
   } else {
-    kd_unit<ROWS, NT>((i64)blockIdx.x * BLOCK + threadIdx.x, (i64)blockIdx.y * ROWS, th_in, th_out, rho_in, rho_out, ld,
-                      grad, ldg, metric, eps, use_pre, pre, use_kick, kick, C2, D);
+    const i64 y = DESC ? (i64)gridDim.y - 1 - blockIdx.y : (i64)blockIdx.y;
+    kd_unit<ROWS, NT>((i64)blockIdx.x * BLOCK + threadIdx.x, y * ROWS, th_in, th_out, rho_in, rho_out, ld, grad, ldg, metric,
+                      eps, use_pre, pre, use_kick, kick, C2, D);
   }
 }
 
@@ -125,14 +130,15 @@ __device__ __forceinline__ void g_unit(i64 c2, i64 d0, const double* th, double*
     }
 }
 
-template <int ROWS, int NT, int BLOCK, bool PERSIST>
+template <int ROWS, int NT, int BLOCK, bool PERSIST, bool DESC = false>
 __global__ __launch_bounds__(BLOCK) void k_g(const double* th, double* g, i64 ld, const double* lam, i64 C2, i64 D) {
   if (PERSIST) {
     const i64 nx = (C2 + BLOCK - 1) / BLOCK, ny = (D + ROWS - 1) / ROWS;
     for (i64 u = blockIdx.x; u < nx * ny; u += gridDim.x)
-      g_unit<ROWS, NT>((u % nx) * BLOCK + threadIdx.x, (u / nx) * ROWS, th, g, ld, lam, C2, D);
+      g_unit<ROWS, NT>((u % nx) * BLOCK + threadIdx.x, (DESC ? ny - 1 - u / nx : u / nx) * ROWS, th, g, ld, lam, C2, D);
   } else {
-    g_unit<ROWS, NT>((i64)blockIdx.x * BLOCK + threadIdx.x, (i64)blockIdx.y * ROWS, th, g, ld, lam, C2, D);
+    const i64 y = DESC ? (i64)gridDim.y - 1 - blockIdx.y : (i64)blockIdx.y;
+    g_unit<ROWS, NT>((i64)blockIdx.x * BLOCK + threadIdx.x, y * ROWS, th, g, ld, lam, C2, D);
   }
 }
 
@@ -145,16 +151,16 @@ struct Args {
 static i64 cdiv(i64 a, i64 b) { return (a + b - 1) / b; }
 constexpr int PGRID = 256 * 8;  // persistent: 8 workgroups per CU
 
-template <int ROWS, int NT, int BLOCK, bool PERSIST>
+template <int ROWS, int NT, int BLOCK, bool PERSIST, bool DESC = false>
 static void launch_kd(const Args& a) {
   dim3 grid = PERSIST ? dim3(PGRID) : dim3((unsigned)cdiv(a.C / 2, BLOCK), (unsigned)cdiv(a.D, ROWS));
-  k_kd<ROWS, NT, BLOCK, PERSIST><<<grid, dim3(BLOCK), 0, a.s>>>(a.th, a.th, a.rho, a.rho, a.ld, a.g, a.ld, nullptr, 0.01, 0,
+  k_kd<ROWS, NT, BLOCK, PERSIST, DESC><<<grid, dim3(BLOCK), 0, a.s>>>(a.th, a.th, a.rho, a.rho, a.ld, a.g, a.ld, nullptr, 0.01, 0,
                                                                  0.0, 1, 0.01, a.C / 2, a.D);
 }
-template <int ROWS, int NT, int BLOCK, bool PERSIST>
+template <int ROWS, int NT, int BLOCK, bool PERSIST, bool DESC = false>
 static void launch_g(const Args& a) {
   dim3 grid = PERSIST ? dim3(PGRID) : dim3((unsigned)cdiv(a.C / 2, BLOCK), (unsigned)cdiv(a.D, ROWS));
-  k_g<ROWS, NT, BLOCK, PERSIST><<<grid, dim3(BLOCK), 0, a.s>>>(a.th, a.g, a.ld, a.lam, a.C / 2, a.D);
+  k_g<ROWS, NT, BLOCK, PERSIST, DESC><<<grid, dim3(BLOCK), 0, a.s>>>(a.th, a.g, a.ld, a.lam, a.C / 2, a.D);
 }
 
 struct Variant {
@@ -183,6 +189,11 @@ static const Variant G[] = {
     V(launch_g, 2, 0, 512, true),
 };
 constexpr int NKD = sizeof(KD) / sizeof(KD[0]), NG = sizeof(G) / sizeof(G[0]);
+// the library's plain pair (KD[1], G[6]) by row order: [0] ascending, [1] descending
+static const Variant KD_ORDER[2] = {{"kd ascending", &launch_kd<1, 0, 256, false, false>},
+                                    {"kd descending", &launch_kd<1, 0, 256, false, true>}};
+static const Variant G_ORDER[2] = {{"g ascending", &launch_g<1, 0, 256, false, false>},
+                                   {"g descending", &launch_g<1, 0, 256, false, true>}};
 
 __global__ void k_fill(double* p, i64 n, double v) {
   for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (i64)gridDim.x * blockDim.x) p[i] = v + 1e-9 * (double)(i & 1023);
@@ -191,7 +202,7 @@ __global__ void k_fill(double* p, i64 n, double v) {
 constexpr int L = 64;
 
 // one trajectory's worth of launches, `reps` times after one warm-up trajectory: out = {median, min, max} ms per trajectory
-static void run_pair(const Args& a, int ik, int ig, int reps, double out[3]) {
+static void run_pair(const Args& a, const Variant& kd, const Variant& g, int reps, double out[3]) {
   hipEvent_t e0, e1;
   CHECK(hipEventCreate(&e0));
   CHECK(hipEventCreate(&e1));
@@ -199,8 +210,8 @@ static void run_pair(const Args& a, int ik, int ig, int reps, double out[3]) {
   for (int r = 0; r < reps + 1; ++r) {
     CHECK(hipEventRecord(e0, a.s));
     for (int n = 0; n < L; ++n) {
-      KD[ik].fn(a);
-      G[ig].fn(a);
+      kd.fn(a);
+      g.fn(a);
     }
     CHECK(hipEventRecord(e1, a.s));
     CHECK(hipEventSynchronize(e1));
@@ -219,7 +230,7 @@ static void run_pair(const Args& a, int ik, int ig, int reps, double out[3]) {
 
 int main(int argc, char** argv) {
   if (argc < 4) {
-    fprintf(stderr, "usage: cache_tile_bench C D ld [kd g]\n");
+    fprintf(stderr, "usage: cache_tile_bench C D ld [kd g | order [kd g]]\n");
     return 1;
   }
   Args a;
@@ -240,10 +251,22 @@ int main(int argc, char** argv) {
   CHECK(hipStreamSynchronize(a.s));
   const double bytes = (double)L * 56.0 * (double)a.C * (double)a.D;
   double o[3];
+  if (argc >= 5 && !strcmp(argv[4], "order")) {  // row orders of the library's plain pair, or one of them; the first
+    const bool one = argc >= 7;                   // combination again at the end: drift of the box
+    if (one && ((atoi(argv[5]) | atoi(argv[6])) & ~1)) return 1;
+    for (int n = one ? 2 * atoi(argv[5]) + atoi(argv[6]) : 0; n < 5; n += one ? 5 : 1) {
+      const int ik = (n >> 1) & 1, ig = n & 1;
+      run_pair(a, KD_ORDER[ik], G_ORDER[ig], one ? 5 : 7, o);
+      printf("ORDER C=%lld D=%lld ld=%lld %-13s + %-12s%s median %.1f us/step (min %.1f max %.1f) %.2f TB/s\n", (long long)a.C,
+             (long long)a.D, (long long)a.ld, KD_ORDER[ik].name, G_ORDER[ig].name, n == 4 ? " (again)" : "", o[0] * 1e3 / L,
+             o[1] * 1e3 / L, o[2] * 1e3 / L, bytes / (o[0] * 1e-3) / 1e12);
+    }
+    return 0;
+  }
   if (argc >= 6) {  // one pair, for a kernel trace
     int ik = atoi(argv[4]), ig = atoi(argv[5]);
     if (ik < 0 || ik >= NKD || ig < 0 || ig >= NG) return 1;
-    run_pair(a, ik, ig, 5, o);
+    run_pair(a, KD[ik], G[ig], 5, o);
     printf("PAIR C=%lld D=%lld ld=%lld %s + %s: median %.4f ms per %d steps (min %.4f max %.4f) = %.1f us/step %.2f TB/s\n",
            (long long)a.C, (long long)a.D, (long long)a.ld, KD[ik].name, G[ig].name, o[0], L, o[1], o[2], o[0] * 1e3 / L,
            bytes / (o[0] * 1e-3) / 1e12);
@@ -253,14 +276,14 @@ int main(int argc, char** argv) {
   int bk = 0, bg = 0;
   for (int ik = 0; ik < NKD; ++ik)
     for (int ig = 0; ig < NG; ++ig) {
-      run_pair(a, ik, ig, 7, o);
+      run_pair(a, KD[ik], G[ig], 7, o);
       printf("SWEEP C=%lld ld=%lld kd=%d g=%d %-32s + %-30s median %.1f us/step (min %.1f max %.1f) %.2f TB/s\n",
              (long long)a.C, (long long)a.ld, ik, ig, KD[ik].name, G[ig].name, o[0] * 1e3 / L, o[1] * 1e3 / L,
              o[2] * 1e3 / L, bytes / (o[0] * 1e-3) / 1e12);
       if (o[0] < best) best = o[0], bk = ik, bg = ig;
     }
   // the reference pair again at the end: drift of the box over the sweep
-  run_pair(a, 0, 0, 7, o);
+  run_pair(a, KD[0], G[0], 7, o);
   printf("SWEEP C=%lld ld=%lld kd=0 g=0 (again) median %.1f us/step (min %.1f max %.1f)\n", (long long)a.C, (long long)a.ld,
          o[0] * 1e3 / L, o[1] * 1e3 / L, o[2] * 1e3 / L);
   printf("BEST %d %d %.1f us/step\n", bk, bg, best * 1e3 / L);
