@@ -631,8 +631,16 @@ int bk_leapfrog_kick_drift(const double* theta_in, double* theta_out, const doub
                                                               use_kick, kick, C / 2, D);                \
   } while (0)
       // (one row per thread puts D into gridDim.y: past its limit the plain launch takes two rows as well)
+      // The in-place step of a resident tile, on a grid of the measured family (gridDim.x a multiple of 8, the rule of
+      // tg_row_group() in bk_targets.hip), takes a cache policy per access: the same shape and bits, theta' the only
+      // array left in the XCDs' L2s for the gradient op that follows (bk_tile_kernels.hpp: k_kick_drift_tile).
+      const bool tile_step = theta_in == theta_out && rho_in == rho_out && arrays == 3 && bk_cdiv(C / 2, KD_BLOCK) % 8 == 0;
       if (bk_streams_past_llc(arrays * C * D))
         BK_KD_LAUNCH(2, true);
+      else if (D <= 65535 && tile_step)
+        bkt::k_kick_drift_tile<BKT_KD_TILE_POLICY>
+            <<<dim3((unsigned)bk_cdiv(C / 2, KD_BLOCK), (unsigned)D), dim3(KD_BLOCK), 0, s>>>(
+                theta_out, rho_out, ld, grad, ldg_d, metric, eps, use_pre, pre, use_kick, kick, C / 2, D);
       else if (D <= 65535)
         BK_KD_LAUNCH(1, false);
       else

@@ -236,7 +236,12 @@ int gauss(const double* theta, double* grad, double* logp, i64 ld, const double*
       // Non-temporal is another 0.8 us faster there but 9 us slower behind a non-temporal kick+drift, and this op does
       // not know its producer.
       dim3 grid((unsigned)bk_cdiv(C / 2, TG_BLOCK), (unsigned)D);
+      // Inside the cache, on a grid that sweeps its rows descending (tg_row_group()), with a cache policy per access: the
+      // gradient is written through the L2s, which keep theta' for the kick+drift that follows (bk_tile_kernels.hpp:
+      // k_gauss_grad_tile; 0.6-0.9 us faster than plain behind a plain kick+drift too).
       if (streams) k_gauss_grad_v2<1, true><<<grid, dim3(TG_BLOCK), 0, s>>>(theta, grad, ld, lam, C / 2, D);
+      else if (grid.x % 8 == 0 && theta != grad)
+        bkt::k_gauss_grad_tile<BKT_GRAD_TILE_POLICY><<<grid, dim3(TG_BLOCK), 0, s>>>(theta, grad, ld, lam, C / 2, D);
       else k_gauss_grad_v2<1, false><<<grid, dim3(TG_BLOCK), 0, s>>>(theta, grad, ld, lam, C / 2, D);
     } else {
       dim3 grid((unsigned)bk_cdiv(C / 2, TG_BLOCK), (unsigned)bk_cdiv(D, 2));

@@ -3,12 +3,15 @@
 // [D][C].  So the launches at a tile's two ends see arrays of DIFFERENT row pitch and of different residency (one side
 // streams from / to HBM, the other is in the cache), and the per-chain reductions run on T chains instead of C.
 //   * kick+drift, blend and select with one pitch per array and one access hint per side;
+//   * the in-place step of a resident tile -- kick+drift and the Gaussian gradient-only kernel -- with a cache policy per
+//     ACCESS (bk_mem_policy.hpp), so that the XCDs' L2s keep theta' across the two launches and nothing else;
 //   * the Gaussian log density (+ gradient) and the finish kernel (half kick + kinetic energy) with enough loads in flight
 //     to run at the cache's rate on a tile's few workgroups -- the SAME summation order as k_gauss_logp(_v2) / k_finish(_v2).
 // Every shape is a template argument: the library instantiates the one it launches (bk_integrator.hip, bk_targets.hip),
 // tools/tile_seam_bench.hip instantiates the candidates it was chosen from (profiles/cache_tiles.md, section 6).
 #pragma once
 #include "bk_common.hpp"
+#include "bk_mem_policy.hpp"
 
 namespace bkt {
 
@@ -66,6 +69,59 @@ __global__ __launch_bounds__(KDL_BLOCK) void k_kick_drift_ld(const double* th_in
     gstore<NO>(rn, reinterpret_cast<dvec2*>(rho_out + d * ld_ro + 2 * c2));
     gstore<NO>(tn, reinterpret_cast<dvec2*>(th_out + d * ld_to + 2 * c2));
   }
+}
+
+// ---- the in-place step of a resident tile, a cache policy per access -------------------------------------------------
+// The plain in-cache pair (k_kick_drift_v2<1, false>, k_gauss_grad_v2<1, false>: two chains per lane, one row per thread,
+// 256 threads, the gradient's rows swept from the last to the first) moves every byte between the XCDs and the Infinity
+// Cache except the lines that survive in the 32 MiB of L2s from one launch to the next, and with plain accesses two thirds
+// of those are lines nobody reads again: rho (the gradient op never touches it) and the gradient kick+drift has just
+// consumed.  Theta' is the one array BOTH kernels read.  With the policies below the L2s hold theta' and little else:
+//   kick+drift   theta load plain, theta store plain (kept);  rho load and store sc1, g load nt (passing through)
+//   gradient     theta load plain (kept);  g store sc1 (written through, the line dropped)
+// 63.9 -> 61.2 us per step of an 8,192 x 1,024 tile, 32.9 -> 29.6 at 4,096 chains, 66.8 -> 64.0 on a tile cut out of a
+// 65,536-chain state (profiles/cache_tiles.md, section 8: 38 combinations).  Either kernel beside the other's plain form is no
+// slower than the plain pair, so neither needs to know its partner.  Measured for grids whose gridDim.x is a multiple of
+// 8 (a column block then meets the same XCD's L2 in both launches: tg_row_group() in bk_targets.hip); the callers route
+// only those here.  Rows are addressed with 32-bit offsets: the callers' footprint rule keeps a row far below 4 GiB.
+// The arithmetic is kd_elem / the gradient expression of k_gauss_grad_v2, operation for operation: the same bits.
+#define BKT_KD_TILE_POLICY bkm::PLAIN, bkm::SC1, bkm::NT, bkm::PLAIN, bkm::SC1  // theta, rho, g loads; theta, rho stores
+#define BKT_GRAD_TILE_POLICY bkm::PLAIN, bkm::SC1                               // theta load; g store
+
+template <int PT, int PR, int PG, int ST, int SR>
+__global__ __launch_bounds__(KDL_BLOCK) void k_kick_drift_tile(double* th, double* rho, i64 ld, const double* grad, i64 ldg,
+                                                               const double* metric, double eps, int use_pre, double pre,
+                                                               int use_kick, double kick, i64 C2, i64 D) {
+  const i64 c2 = (i64)blockIdx.x * KDL_BLOCK + threadIdx.x, d = blockIdx.y;
+  if (c2 >= C2) return;
+  const uint32_t bytes = (uint32_t)(16 * C2), c = (uint32_t)c2;
+  const bkm::Row rt = {th + d * ld, bytes}, rr = {rho + d * ld, bytes}, rg = {grad + d * ldg, bytes};
+  const dvec2 t = bkm::load16<PT>(rt, c), r = bkm::load16<PR>(rr, c), g = bkm::load16<PG>(rg, c);
+  const double m = metric ? metric[d] : 1.0;
+  dvec2 rn, tn;
+  double rx, ry;
+  tn.x = kd_elem(t.x, r.x, g.x, m, metric != nullptr, eps, use_pre, pre, use_kick, kick, rx);
+  tn.y = kd_elem(t.y, r.y, g.y, m, metric != nullptr, eps, use_pre, pre, use_kick, kick, ry);
+  rn.x = rx;
+  rn.y = ry;
+  bkm::store16<SR>(rn, rr, c);
+  bkm::store16<ST>(tn, rt, c);
+}
+
+// grad = -(lam*theta)  (lam NULL -> grad = -theta); row gridDim.y - 1 - blockIdx.y
+template <int PT, int SG>
+__global__ __launch_bounds__(KDL_BLOCK) void k_gauss_grad_tile(const double* th, double* g, i64 ld, const double* lam, i64 C2,
+                                                               i64 D) {
+  const i64 c2 = (i64)blockIdx.x * KDL_BLOCK + threadIdx.x, d = (i64)gridDim.y - 1 - blockIdx.y;
+  if (c2 >= C2) return;
+  const uint32_t bytes = (uint32_t)(16 * C2), c = (uint32_t)c2;
+  const bkm::Row rt = {th + d * ld, bytes}, rg = {g + d * ld, bytes};
+  const dvec2 t = bkm::load16<PT>(rt, c);
+  const double l = lam ? lam[d] : 1.0;
+  dvec2 o;
+  o.x = lam ? -(l * t.x) : -t.x;
+  o.y = lam ? -(l * t.y) : -t.y;
+  bkm::store16<SG>(o, rg, c);
 }
 
 // any pitches, any alignment, any layout of the gradient: one chain per lane

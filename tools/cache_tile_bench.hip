@@ -1,13 +1,19 @@
 // Stand-alone measurement behind profiles/cache_tiles.md: shapes of kick+drift (bk_integrator.hip: k_kick_drift_v2) and of
 // the Gaussian gradient op (bk_targets.hip: k_gauss_grad_v2) on one Infinity-Cache tile.  A trajectory's worth of launches --
 // 64 alternating (kick+drift, gradient) pairs, in place, on columns [0, C) of a [D][ld] state -- timed by HIP events, for
-// every pair of the variants listed below; the kernels are copies of the library's with the shape as template arguments.
+// every pair of the variants listed below; the kernels are copies of the library's with the shape as template arguments
+// (the policy mode instantiates the library's own templates of csrc/bk_tile_kernels.hpp).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off tools/cache_tile_bench.hip -o cache_tile_bench
 //   cache_tile_bench C D ld              every pair (a tile of a 65,536-chain state: 8192 1024 65536)
 //   cache_tile_bench C D ld KD G         one pair, e.g. under rocprofv3 --kernel-trace --stats
 //   cache_tile_bench C D ld order        the library's plain pair with each kernel's rows swept ascending or descending: the
 //                                        four combinations, then the first again (profiles/cache_tiles.md section 7)
 //   cache_tile_bench C D ld order KD G   one of them (0 ascending, 1 descending), e.g. under rocprofv3 --pmc FETCH_SIZE
+//   cache_tile_bench C D ld policy       the library's plain pair (gradient rows descending) with a cache policy per ACCESS
+//                                        (csrc/bk_mem_policy.hpp): the candidates of POLICY[] below, the all-plain pair first
+//                                        and again last; every candidate starts from the same state and prints a checksum of
+//                                        what it leaves, which must be the same in every line (section 8)
+//   cache_tile_bench C D ld policy KD G  candidate KD's kick+drift with candidate G's gradient kernel, e.g. under rocprofv3
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -15,6 +21,8 @@
 #include <string.h>
 #include <algorithm>
 #include <vector>
+
+#include "../bayes-kit_amd/csrc/bk_tile_kernels.hpp"  // k_kick_drift_tile, k_gauss_grad_tile (+ bk_mem_policy.hpp): policy mode
 
 typedef int64_t i64;
 typedef double dvec2 __attribute__((ext_vector_type(2)));
@@ -195,6 +203,71 @@ static const Variant KD_ORDER[2] = {{"kd ascending", &launch_kd<1, 0, 256, false
 static const Variant G_ORDER[2] = {{"g ascending", &launch_g<1, 0, 256, false, false>},
                                    {"g descending", &launch_g<1, 0, 256, false, true>}};
 
+// ---- a cache policy per access: the library's templates (bk_tile_kernels.hpp), kick+drift ascending, the gradient descending
+template <int PT, int PR, int PG, int ST, int SR>
+static void launch_kd_pol(const Args& a) {
+  bkt::k_kick_drift_tile<PT, PR, PG, ST, SR><<<dim3((unsigned)cdiv(a.C / 2, 256), (unsigned)a.D), dim3(256), 0, a.s>>>(
+      a.th, a.rho, a.ld, a.g, a.ld, nullptr, 0.01, 0, 0.0, 1, 0.01, a.C / 2, a.D);
+}
+template <int PT, int SG>
+static void launch_g_pol(const Args& a) {
+  bkt::k_gauss_grad_tile<PT, SG><<<dim3((unsigned)cdiv(a.C / 2, 256), (unsigned)a.D), dim3(256), 0, a.s>>>(a.th, a.g, a.ld, a.lam,
+                                                                                                       a.C / 2, a.D);
+}
+
+struct PolicyPair {
+  const char* name;
+  void (*kd)(const Args&);
+  void (*g)(const Args&);
+};
+constexpr int P_ = bkm::PLAIN, N_ = bkm::NT, S1 = bkm::SC1, S01 = bkm::SC0_SC1, S01N = bkm::SC0_SC1_NT;
+// kick+drift <theta load, rho load, g load, theta store, rho store> + gradient <theta load, g store>
+#define PP(name, a, b, c, d, e, f, g) {name, &launch_kd_pol<a, b, c, d, e>, &launch_g_pol<f, g>}
+static const PolicyPair POLICY[] = {
+    PP("0 all plain", P_, P_, P_, P_, P_, P_, P_),
+    PP("1 g load nt", P_, P_, N_, P_, P_, P_, P_),
+    PP("2 rho load+store nt", P_, N_, P_, P_, N_, P_, P_),
+    PP("3 g load, rho load+store nt", P_, N_, N_, P_, N_, P_, P_),
+    PP("4 g load sc1", P_, P_, S1, P_, P_, P_, P_),
+    PP("5 rho load+store sc1", P_, S1, P_, P_, S1, P_, P_),
+    PP("6 g load, rho load+store sc1", P_, S1, S1, P_, S1, P_, P_),
+    PP("7 g load sc0sc1", P_, P_, S01, P_, P_, P_, P_),
+    PP("8 rho load+store sc0sc1", P_, S01, P_, P_, S01, P_, P_),
+    PP("9 g load, rho load+store sc0sc1", P_, S01, S01, P_, S01, P_, P_),
+    PP("10a all stores sc1", P_, P_, P_, S1, S1, P_, S1),
+    PP("10b all stores sc0sc1", P_, P_, P_, S01, S01, P_, S01),
+    PP("11a 1 + theta, rho, g stores sc1", P_, P_, N_, S1, S1, P_, S1),
+    PP("11b 2 + theta, g stores sc1", P_, N_, P_, S1, N_, P_, S1),
+    PP("11c 3 + theta, g stores sc1", P_, N_, N_, S1, N_, P_, S1),
+    PP("11d 3 + g store sc1", P_, N_, N_, P_, N_, P_, S1),
+    PP("11e 6 + theta, g stores sc1", P_, S1, S1, S1, S1, P_, S1),
+    PP("11f g load nt, rho load nt, rho store sc1", P_, N_, N_, P_, S1, P_, P_),
+    PP("12 theta load nt (control)", N_, P_, P_, P_, P_, P_, P_),
+    PP("13 g load sc0sc1nt", P_, P_, S01N, P_, P_, P_, P_),
+    PP("14 rho load+store sc0sc1nt", P_, S01N, P_, P_, S01N, P_, P_),
+    PP("15 g load, rho load+store sc0sc1nt", P_, S01N, S01N, P_, S01N, P_, P_),
+    PP("16 rho store only nt", P_, P_, P_, P_, N_, P_, P_),
+    PP("17 rho store only sc1", P_, P_, P_, P_, S1, P_, P_),
+    PP("18 g store sc1", P_, P_, P_, P_, P_, P_, S1),
+    PP("19 g store nt", P_, P_, P_, P_, P_, P_, N_),
+    PP("20 11d, rho store sc1", P_, N_, N_, P_, S1, P_, S1),
+    PP("21 g load nt + g store sc1", P_, P_, N_, P_, P_, P_, S1),
+    PP("22 2 + g store sc1", P_, N_, P_, P_, N_, P_, S1),
+    PP("23 11d, g load sc1", P_, N_, S1, P_, N_, P_, S1),
+    PP("24 11d, g store sc0sc1", P_, N_, N_, P_, N_, P_, S01),
+    PP("25 11d, every nt as sc0sc1nt", P_, S01N, S01N, P_, S01N, P_, S01),
+    PP("26 11d, rho load plain", P_, P_, N_, P_, N_, P_, S1),
+    PP("27 11d, g store sc0sc1nt", P_, N_, N_, P_, N_, P_, S01N),
+    PP("28 11d, rho load+store sc1", P_, S1, N_, P_, S1, P_, S1),
+    PP("30 kick+drift of 28, gradient plain", P_, S1, N_, P_, S1, P_, P_),
+    PP("31 rho load nt, rho store sc1", P_, N_, P_, P_, S1, P_, P_),
+    PP("32 31 + g store sc1", P_, N_, P_, P_, S1, P_, S1),
+    PP("33 5 + g store sc1", P_, S1, P_, P_, S1, P_, S1),
+    PP("0 all plain (again)", P_, P_, P_, P_, P_, P_, P_),
+};
+#undef PP
+constexpr int NPOL = sizeof(POLICY) / sizeof(POLICY[0]);
+
 __global__ void k_fill(double* p, i64 n, double v) {
   for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (i64)gridDim.x * blockDim.x) p[i] = v + 1e-9 * (double)(i & 1023);
 }
@@ -230,7 +303,7 @@ static void run_pair(const Args& a, const Variant& kd, const Variant& g, int rep
 
 int main(int argc, char** argv) {
   if (argc < 4) {
-    fprintf(stderr, "usage: cache_tile_bench C D ld [kd g | order [kd g]]\n");
+    fprintf(stderr, "usage: cache_tile_bench C D ld [kd g | order [kd g] | policy [kd g]]\n");
     return 1;
   }
   Args a;
@@ -239,7 +312,7 @@ int main(int argc, char** argv) {
   a.ld = atoll(argv[3]);
   if (a.C % 2 || a.ld % 2 || a.ld < a.C || a.C <= 0 || a.D <= 0) return 1;
   CHECK(hipStreamCreate(&a.s));
-  const i64 n = a.D * a.ld;
+  const i64 n = a.D * a.ld, n_total = n;
   CHECK(hipMalloc(&a.th, n * 8));
   CHECK(hipMalloc(&a.rho, n * 8));
   CHECK(hipMalloc(&a.g, n * 8));
@@ -251,6 +324,37 @@ int main(int argc, char** argv) {
   CHECK(hipStreamSynchronize(a.s));
   const double bytes = (double)L * 56.0 * (double)a.C * (double)a.D;
   double o[3];
+  if (argc >= 5 && !strcmp(argv[4], "policy")) {  // a cache policy per access; every candidate from the same state
+    const bool one = argc >= 7;
+    const int k0 = one ? atoi(argv[5]) : 0, g0 = one ? atoi(argv[6]) : 0;
+    if (k0 < 0 || k0 >= NPOL || g0 < 0 || g0 >= NPOL) return 1;
+    std::vector<double> h(3 * 2048);
+    const i64 nh = std::min<i64>(2048, a.C);
+    for (int n = one ? k0 : 0; n < NPOL; n += one ? NPOL : 1) {
+      k_fill<<<1024, 256, 0, a.s>>>(a.th, n_total, 0.5);
+      k_fill<<<1024, 256, 0, a.s>>>(a.rho, n_total, 0.25);
+      k_fill<<<1024, 256, 0, a.s>>>(a.g, n_total, 0.125);
+      const Variant kd = {POLICY[n].name, POLICY[n].kd}, g = {POLICY[one ? g0 : n].name, POLICY[one ? g0 : n].g};
+      run_pair(a, kd, g, one ? 5 : 7, o);
+      // what the candidate left in the first columns of the last row: the same bits for every policy
+      const i64 off = (a.D - 1) * a.ld;
+      CHECK(hipMemcpy(h.data(), a.th + off, nh * 8, hipMemcpyDeviceToHost));
+      CHECK(hipMemcpy(h.data() + 2048, a.rho + off, nh * 8, hipMemcpyDeviceToHost));
+      CHECK(hipMemcpy(h.data() + 4096, a.g + off, nh * 8, hipMemcpyDeviceToHost));
+      uint64_t sum = 1469598103934665603ull;
+      for (int j = 0; j < 3; ++j)
+        for (i64 i = 0; i < nh; ++i) {
+          uint64_t b;
+          memcpy(&b, &h[j * 2048 + i], 8);
+          sum = (sum ^ b) * 1099511628211ull;
+        }
+      printf("POLICY C=%lld D=%lld ld=%lld %-42s median %.2f us/step (min %.2f max %.2f) %.2f TB/s  sum %016llx\n",
+             (long long)a.C, (long long)a.D, (long long)a.ld, one ? "(kd of KD, g of G)" : POLICY[n].name, o[0] * 1e3 / L,
+             o[1] * 1e3 / L, o[2] * 1e3 / L, bytes / (o[0] * 1e-3) / 1e12, (unsigned long long)sum);
+      fflush(stdout);
+    }
+    return 0;
+  }
   if (argc >= 5 && !strcmp(argv[4], "order")) {  // row orders of the library's plain pair, or one of them; the first
     const bool one = argc >= 7;                   // combination again at the end: drift of the box
     if (one && ((atoi(argv[5]) | atoi(argv[6])) & ~1)) return 1;
