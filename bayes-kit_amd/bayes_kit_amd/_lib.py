@@ -45,6 +45,7 @@ SIGNATURES = {
     "bk_mh_accept": [c_int, P, P, P, P, P, P, P, P, I, P],
     "bk_select_columns": [P, P, P, P, P, P, I, I, I, P],
     "bk_blend_columns": [P, P, P, P, I, I, I, P],
+    "bk_stretch_propose": [P, I, I, I, I, I, P, P, F, F, P, I, P, P, I, P],
     "bk_leapfrog_kick_drift_ld": [P, I, P, I, P, I, P, I, P, I, I, P, F, c_int, F, c_int, F, I, I, P],
     "bk_blend_columns_ld": [P, P, I, P, I, P, I, I, I, P],
     "bk_select_columns_ld": [P, P, I, P, I, I, I, P],
@@ -452,6 +453,17 @@ class Ops:
         assert copy0 is None or _ld(copy0) == ld
         self._call("bk_select_columns", ptr(mask), ptr(dst0), ptr(src0), ptr(dst1), ptr(src1), ptr(copy0), ld,
                    C, D, self._s())
+
+    def stretch_propose(self, theta, col_act, col_oth, n, H, u_j, u_z, inv_sqrt_a, sqrt_a, theta_prop, zterm, partner):
+        """The stretch move of the n active walkers in columns [col_act, col_act + n) of the state `theta` against the other
+        halves of their ensembles, columns [col_oth, col_oth + n), H walkers per ensemble half: theta_prop [D, n] (own pitch),
+        zterm [n] = (D - 1) log z, partner [n] (int32 column of theta).  bk_stretch_propose."""
+        D = theta.shape[0]
+        assert tuple(theta_prop.shape) == (D, n) and partner.dtype == torch.int32
+        assert min(u_j.numel(), u_z.numel(), zterm.numel(), partner.numel()) >= n
+        self._call("bk_stretch_propose", ptr(theta), _ld(theta), int(col_act), int(col_oth), int(n), int(H), ptr(u_j),
+                   ptr(u_z), float(inv_sqrt_a), float(sqrt_a), ptr(theta_prop), _ld(theta_prop), ptr(zterm), ptr(partner), D,
+                   self._s())
 
     # -- delayed rejection ---------------------------------------------------------------------
     # n_dev (optional, everywhere below): int32 device tensor [1] holding the number of lanes really

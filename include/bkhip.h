@@ -250,6 +250,27 @@ int bk_select_columns(const uint8_t* mask, double* dst0, const double* src0,
 int bk_blend_columns(const uint8_t* mask, const double* a, const double* b, double* out,
                      int64_t ld, int64_t C, int64_t D, void* stream);
 
+/* ---- affine-invariant ensemble sampler: the stretch move (Goodman & Weare 2010; ensemble.py:47-65) -----
+ * theta [D][ld] holds walkers in columns.  The n ACTIVE walkers are columns [col_act, col_act + n); they belong to
+ * n / H ensembles of H consecutive columns each, and the other half of the e-th of them is columns
+ * [col_oth + e*H, col_oth + (e + 1)*H).  For active walker k (ensemble e = k / H), from its uniforms u_j[k], u_z[k]:
+ *     j            = col_oth + e*H + min(floor(u_j[k] * H), H - 1)       np.random.choice(other half), ensemble.py:60
+ *     r            = inv_sqrt_a + (sqrt_a - inv_sqrt_a) * u_z[k] ;  z = r * r                         ensemble.py:49
+ *     theta_prop[d*ldp + k] = theta[d*ld + j] + z * (theta[d*ld + col_act + k] - theta[d*ld + j])     ensemble.py:53
+ *     zterm[k]     = (D - 1) * log(z)             ensemble.py:54 (the device log of bk_log_uniform)
+ *     partner[k]   = j
+ * Every operation is rounded on its own.  floor(u_j * H) is clamped to [0, H - 1], so any value of u_j gives a column
+ * of the other half.  theta is only read; theta_prop must not overlap it.  Follow with the model's log density at
+ * theta_prop and bk_mh_accept(BK_ACCEPT_MALA, lp, NULL, lp_prop, zterm, log_u, ...), bk_select_columns.
+ * The two forms by shape: n, ld, ldp even with theta + col_act and theta_prop 16-byte aligned -> two walkers per lane;
+ * anything else one walker per lane; same results.  HBM traffic 24*D bytes per active walker when the gather of theta_j
+ * is served from cache (for one d all of them fall into n*8 contiguous bytes).
+ * BK_E_ARG: a null pointer, n < 0, D < 0, a negative column, H < 1, n % H != 0, ld < max(col_act, col_oth) + n, ldp < n,
+ * D > 262,140; decided before any HIP call.  n == 0 or D == 0: BK_OK, nothing launched. */
+int bk_stretch_propose(const double* theta, int64_t ld, int64_t col_act, int64_t col_oth, int64_t n, int64_t H,
+                       const double* u_j, const double* u_z, double inv_sqrt_a, double sqrt_a, double* theta_prop,
+                       int64_t ldp, double* zterm, int32_t* partner, int64_t D, void* stream);
+
 /* ---- the same three operations with ONE ROW PITCH PER ARRAY (the tile-major HMC schedule) ---------------
  * A tile of T chains keeps its proposal, momentum and trajectory gradient in contiguous [D][T] arrays that stay
  * in the Infinity Cache, while the state, the generator's momentum and the cached gradient are columns of [D][C]
