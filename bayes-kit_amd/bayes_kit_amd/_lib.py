@@ -92,6 +92,9 @@ SIGNATURES = {
     "bk_dense_metric_apply": [P, I, P, P, I, I, I, P],
     "bk_gemm_chains": [P, I, I, I, P, I, P, I, I, P, I, P],
     "bk_gemm_chains_work_elems": [I, I, I],
+    "bk_cov_k_chunk": [I],
+    "bk_cov_accumulate_work_elems": [I, I],
+    "bk_cov_accumulate": [P, I, I, I, P, P, I, P, P, I, P],
     "bk_logistic_residual": [P, I, P, P, I, I, I, P],
     "bk_logistic_finish": [P, P, I, P, I, F, F, P, P, P, I, I, P],
     "bk_dot_columns": [P, P, I, F, P, I, I, P],
@@ -132,7 +135,7 @@ SIGNATURES = {
     "bk_host_log1p": [F],
     "bk_host_exp": [F],
 }
-_RESTYPE = {"bk_gemm_chains_work_elems": c_int64, "bk_host_log1p": c_double, "bk_host_exp": c_double, "bk_refresh_work_elems": c_int64, "bk_sort_by_key_work_bytes": c_int64,
+_RESTYPE = {"bk_gemm_chains_work_elems": c_int64, "bk_cov_k_chunk": c_int64, "bk_cov_accumulate_work_elems": c_int64, "bk_host_log1p": c_double, "bk_host_exp": c_double, "bk_refresh_work_elems": c_int64, "bk_sort_by_key_work_bytes": c_int64,
              "bk_autocorr_fft_work_bytes": c_int64, "bk_ess_multi_work_bytes": c_int64, "bk_ess_lag_sums_max_half": c_int64}
 
 
@@ -831,6 +834,23 @@ class Ops:
         D, C = X.shape
         assert _ld(Y) == _ld(X)
         self._call("bk_dense_metric_apply", ptr(M), _ld(M), ptr(X), ptr(Y), _ld(X), C, D, self._s())
+
+    def cov_k_chunk(self, D):
+        """Chains per chunk of cov_accumulate's split (a function of D only; slabs are whole chunks)."""
+        return int(self.lib.bk_cov_k_chunk(D))
+
+    def cov_work(self, D, C):
+        """Slab scratch for cov_accumulate (a tensor of bk_cov_accumulate_work_elems doubles)."""
+        n = int(self.lib.bk_cov_accumulate_work_elems(D, C))
+        return torch.empty(max(n, 1), dtype=torch.float64, device=self.device)
+
+    def cov_accumulate(self, X, center, S, s, work):
+        """S[D, D] += (X - center 1^T)(X - center 1^T)^T, s[D] += rowsum(X - center 1^T) for X[D, C] (center None: zeros)
+        on the fp64 matrix cores; only S's lower triangle is read, both triangles are written."""
+        D, C = X.shape
+        assert S.shape == (D, D) and s.numel() == D and (center is None or center.numel() == D)
+        self._call("bk_cov_accumulate", ptr(X), _ld(X), C, D, ptr(center), ptr(S), _ld(S), ptr(s), ptr(work),
+                   0 if work is None else work.numel(), self._s())
 
     def gemm_chains_work(self, R, K, C):
         """Split-K scratch for gemm_chains (a tensor of bk_gemm_chains_work_elems doubles, or None: no split)."""

@@ -173,6 +173,97 @@ class RunningMoments:
         self.n = int(sd["n"])
 
 
+class RunningCovariance:
+    """Streaming D x D covariance of the draws of ALL chains pooled -- the full-matrix counterpart of RunningMoments,
+    fed one draw at a time.  Kept as the shifted sums S = sum (x - c)(x - c)^T and s = sum (x - c) over the n points
+    seen (bk_cov_accumulate: one fp64 MFMA pass over the draw, D^2 C flop), with the centre c fixed by the FIRST update
+    after construction or reset() to that draw's cross-chain mean (the row sums of bk_rhat_partials, divided on the
+    device): the draws of a warmup window stay near it, so (S - s s^T / n) / (n - 1) does not cancel.  Sized for the dense
+    metric's range, D up to a few hundred (or modest chain counts): the state is D^2 doubles, an update at
+    1,024 x 65,536 chains is of the order of a second.  Non-finite chain states poison the estimate, as they do
+    RunningMoments'; they are not filtered.
+
+    Across ranks every rank must shift by the same vector: pass ``group`` to update() and the first update takes the mean
+    over the chains of all ranks (sums gathered in rank order)."""
+
+    def __init__(self, D: int, ops=None):
+        self._ops = _ops(ops)
+        dev = self._ops.device
+        self._D = int(D)
+        self.S = torch.zeros((self._D, self._D), dtype=torch.float64, device=dev)
+        self.s = torch.zeros(self._D, dtype=torch.float64, device=dev)
+        self.center = torch.zeros(self._D, dtype=torch.float64, device=dev)
+        self.n = 0
+        self._work, self._work_C = None, -1
+
+    def update(self, theta, layout=None, group=None) -> None:
+        """theta: the sampler's draw, the engine's [D, C] buffer or the (C, D) view returned by ``sample()`` (as
+        RunningMoments.update; C may differ between updates).  n += C."""
+        D = self._D
+        if theta.dim() != 2:
+            raise ValueError(f"expected a 2-D draw, got shape {tuple(theta.shape)}")
+        if layout is None:  # (the chain count is whichever extent is not D; a square draw is told apart by _as_dc)
+            C = theta.shape[1] if (theta.shape[0] == D and theta.shape[1] != D) else theta.shape[0]
+        else:
+            C = theta.shape[1] if layout == "dc" else theta.shape[0]
+        t = _as_dc(theta, D, C, layout)
+        if (t.shape[1] > 1 and t.stride(1) != 1) or t.dtype != torch.float64:
+            t = t.to(torch.float64).contiguous()
+        ops = self._ops
+        if self.n == 0:
+            part = torch.zeros(3 * D + 1, dtype=torch.float64, device=t.device)
+            ops.rhat_partials(t, t, 2, None, part)  # part[0:D] = the row sums over this rank's chains
+            part[3 * D] = float(C)
+            tot = _gather_sum(part, group)
+            self.center.copy_(tot[0:D] / tot[3 * D:3 * D + 1])  # (divided as a TENSOR: the same doubles on every device)
+        if self._work_C != C:
+            self._work, self._work_C = ops.cov_work(D, C), C
+        ops.cov_accumulate(t, self.center, self.S, self.s, self._work)
+        self.n += C
+
+    def _totals(self, group):
+        D = self._D
+        if self.n == 0 and not _bkdist.collectives_active(group):
+            raise ValueError("covariance of no draws")
+        pack = torch.cat([self.S.reshape(-1), self.s, torch.tensor([float(self.n)], dtype=torch.float64,
+                                                                    device=self.S.device)])
+        tot = _gather_sum(pack, group)
+        return tot[0:D * D].reshape(D, D), tot[D * D:D * D + D], tot[D * D + D:D * D + D + 1]
+
+    def covariance(self, group=None) -> torch.Tensor:
+        """Device tensor [D, D]: (S - s s^T / n) / (n - 1) with S, s, n summed over the ranks of `group` in rank order
+        (every rank must have shifted by the same centre: update(..., group=group)).  Exactly symmetric."""
+        S, s, n = self._totals(group)
+        if float(n) < 2:
+            raise ValueError("covariance needs at least 2 points")
+        return (S - torch.outer(s, s) / n) / (n - 1.0)
+
+    def mean(self, group=None) -> torch.Tensor:
+        """Device tensor [D]: the mean of all points seen, center + s / n."""
+        _, s, n = self._totals(group)
+        return self.center + s / n
+
+    def reset(self) -> None:
+        """Forget every draw; the next update fixes a new centre."""
+        self.S.zero_()
+        self.s.zero_()
+        self.center.zero_()
+        self.n = 0
+
+    def state_dict(self):
+        return {"n": self.n, "S": self.S.detach().cpu().clone(), "s": self.s.detach().cpu().clone(),
+                "center": self.center.detach().cpu().clone()}
+
+    def load_state_dict(self, sd):
+        if tuple(sd["S"].shape) != tuple(self.S.shape):
+            raise ValueError(f"checkpoint holds a scatter matrix of shape {tuple(sd['S'].shape)}, expected "
+                             f"{tuple(self.S.shape)}")
+        self.S.copy_(sd["S"].to(self.S.device))
+        self.s.copy_(sd["s"].to(self.s.device))
+        self.center.copy_(sd["center"].to(self.center.device))
+        self.n = int(sd["n"])
+
+
 class DrawRecorder:
     """Draw storage for post-processing: the full series of a few tracked
     coordinates (and the returned log density) as ``[K, N, C]`` -- draw-major, chain-contiguous,

@@ -242,6 +242,21 @@ class HMCDiag(ManyChainSampler):
                 torch.cuda.current_stream().wait_event(self._pf_event)
             self._pf_ready, self._pf_event = False, None
 
+    def _rewind_prefetch(self):
+        """Drop randomness generated ahead (prefetch_rng) AND take the stream back to where its generation began, as
+        set_precond_diag does: the next draw generates it again, and the stream position stays that of a sampler
+        without prefetch_rng."""
+        if getattr(self, "_prefetch", False) and self._pf_ready:
+            if self._pf_event is not None:
+                torch.cuda.current_stream().wait_event(self._pf_event)
+            self._rng_state.copy_(self._rng_logical if self._snap is None else self._snap[self._pf_slot])
+            self._pf_ready, self._pf_event = False, None
+
+    @property
+    def metric_dense(self):
+        """The dense metric as a host array (None when the sampler was built without one)."""
+        return None if self._M is None else self._M.cpu().numpy().copy()
+
     # -- the proper diagonal preconditioner -----------------------------------------------------------
     def _install_precond(self, v):
         """Validate v and form {v, sqrt(v), 1/v} on the device, in place once the buffer exists (a captured hipGraph
@@ -580,7 +595,8 @@ class HMCDiag(ManyChainSampler):
 
     def _state_extra(self):
         return {"stepsize": float(self._stepsize), "precond_diag": None if self._pd is None else self._pd[0].cpu().clone(),
-                "trajectory_length": self._T, "max_steps": self._max_steps, "jitter_n": self._jitter_n}
+                "trajectory_length": self._T, "max_steps": self._max_steps, "jitter_n": self._jitter_n,
+                "metric_dense": None if self._M is None else self._M.cpu().clone()}
 
     def _load_extra(self, extra):
         # (checkpoints written before the step size and the preconditioner were carried hold neither: nothing changes)
@@ -598,6 +614,12 @@ class HMCDiag(ManyChainSampler):
                 self._leave_whole_draw()
         elif self._pd is not None and "precond_diag" in extra:
             raise ValueError("checkpoint was written without precond_diag, this sampler has one")
+        Md = extra.get("metric_dense")  # (older checkpoints carry none: the sampler keeps what it was built with)
+        if Md is not None:
+            if self._M is None:
+                raise ValueError("checkpoint holds metric_dense, this sampler was built without one (build it with "
+                                 "metric_dense=np.eye(D))")
+            self._install_metric_dense(Md)
 
     def _after_load(self):
         # drop any randomness generated ahead: it is regenerated from the restored stream
@@ -711,6 +733,19 @@ class HMCDiag(ManyChainSampler):
         x chains, becomes the preconditioner (set_precond_diag), the moments are reset and the step size restarts from
         its averaged iterate.
 
+        Dense metric (adapt_metric="dense"; accepted only on a sampler built with ``metric_dense=``, np.eye(D) being the
+        natural start): the same windows and the same step-size schedule, with the D x D covariance of the state of ALL
+        chains pooled in place of the variances -- diagnostics.RunningCovariance, one bk_cov_accumulate per draw inside a
+        window (an fp64 MFMA pass of D^2 C flop: half of one of the 2L + 2 matrix applications a dense draw pays) around
+        the first draw's cross-chain mean, common to all ranks.  At a window's end
+        M = N/(N+5) * cov + 1e-3 * 5/(N+5) * I is installed with set_metric_dense (Cholesky factor and inverse on the host,
+        as at construction: three times per warmup) and the accumulator is reset.  A momentum generated ahead with the old
+        metric (prefetch_rng) is generated again from the stream position it started at, so the stream ends where a
+        sampler without prefetch_rng leaves it.  The report gains ``metric_dense`` (host copy); ``precond_diag`` stays None.
+        Meant for D up to a few hundred, or for modest chain counts: at 1,024 x 65,536 chains an update is of the order of
+        a second, and so is every leapfrog step of a dense draw.  Non-finite chain states poison the estimate exactly as
+        they do the diagonal one; they are not filtered.  Cannot be combined with adapt_trajectory.
+
         Trajectory length (adapt_trajectory=True; `steps` is not adapted otherwise): ChEES-HMC (Hoffman, Radul, Sountsov
         2021).  Every warmup draw is jittered around the integration time T (see ``trajectory_length``; it starts from the
         sampler's, or steps * stepsize), and adapt.TrajectoryAdam ascends log T along the gradient of
@@ -739,14 +774,21 @@ class HMCDiag(ManyChainSampler):
         world sizes end at different, equally valid adaptations (observed: eps 0.647 against 0.675, v within 3 % of each
         other and of the truth)."""
         from .adapt import DualAveraging, TrajectoryAdam, warmup_windows
-        from .diagnostics import RunningMoments, _gather_sum, pooled_variance_from_moments
+        from .diagnostics import RunningCovariance, RunningMoments, _gather_sum, pooled_variance_from_moments
 
         draws = int(draws)
         if draws < 1:
             raise ValueError(f"warmup: draws must be >= 1, got {draws}")
         if not 0.0 < float(target_accept) < 1.0:
             raise ValueError(f"warmup: target_accept must be inside (0, 1), got {target_accept}")
-        if adapt_metric and (self._M is not None or (self._pd is None and self._metric_dev is not None)):
+        dense = isinstance(adapt_metric, str)
+        if dense:
+            if adapt_metric != "dense":
+                raise ValueError(f"warmup: adapt_metric must be True, False or 'dense', got {adapt_metric!r}")
+            if self._M is None:
+                raise ValueError("warmup: adapt_metric='dense' estimates metric_dense and is accepted only on a sampler "
+                                 "built with metric_dense= (np.eye(D) is the natural start)")
+        elif adapt_metric and (self._M is not None or (self._pd is None and self._metric_dev is not None)):
             raise ValueError("warmup: adapt_metric=True estimates precond_diag, which cannot be combined with "
                              "metric_diag / metric_dense (pass adapt_metric=False to tune the step size alone)")
         if adapt_trajectory:
@@ -769,7 +811,8 @@ class HMCDiag(ManyChainSampler):
         if not adapt_metric:
             ends = []
         da = DualAveraging(float(self._stepsize), float(target_accept))
-        mom = RunningMoments(D, C, ops) if ends else None
+        mom = RunningMoments(D, C, ops) if (ends and not dense) else None
+        cov = RunningCovariance(D, ops) if (ends and dense) else None
         # {sum of the statistic, NaN chains, chains} and, adapting the trajectory, {sum of w g, chains with a non-finite g}
         self._stat = torch.zeros(5 if adapt_trajectory else 3, dtype=torch.float64, device=dev)
         self._stat[2] = float(C)
@@ -804,6 +847,8 @@ class HMCDiag(ManyChainSampler):
                 nan_chains += int(tot[1])
                 if mom is not None and init <= it < draws - term:
                     mom.update(self._theta_dc, layout="dc")
+                if cov is not None and init <= it < draws - term:
+                    cov.update(self._theta_dc, layout="dc", group=group)
                 eps = da.step(alpha)
                 if ta is not None:
                     nonfinite += int(tot[4])
@@ -813,7 +858,16 @@ class HMCDiag(ManyChainSampler):
                         ta.restart()  # (the geometry changes with the metric below)
                     if it + 1 == draws:
                         self._T = ta.final()
-                if it + 1 in ends:
+                if it + 1 in ends and cov is not None:
+                    n_eff = float(cov.n // C) * chains_total
+                    Mn = n_eff / (n_eff + 5.0) * cov.covariance(group)
+                    Mn.diagonal().add_(1e-3 * 5.0 / (n_eff + 5.0))
+                    self._rewind_prefetch()  # (the momentum generated ahead carries the old metric: generate it again)
+                    self.set_metric_dense(Mn)
+                    cov.reset()
+                    eps = da.final()
+                    da.restart(eps)
+                elif it + 1 in ends:
                     n_eff = float(mom.n) * chains_total
                     var = pooled_variance_from_moments(mom.mean, mom.m2, mom.n, ops, group)
                     self.set_precond_diag(n_eff / (n_eff + 5.0) * var + 1e-3 * 5.0 / (n_eff + 5.0))
@@ -825,12 +879,14 @@ class HMCDiag(ManyChainSampler):
                 self._stepsize = eps
         finally:
             self._stat, self._stat_work, self._chees, self._rho_cur = None, None, None, None
-            del mom
+            del mom, cov
             self._drop_graphs()
             if was_fused and (self._pd is None or hasattr(self._model, "bk_hmc_draw_precond")):
                 self._enter_whole_draw()
         rep = {"stepsize": float(self._stepsize), "precond_diag": self.precond_diag, "eps": eps_hist, "alpha": alpha_hist,
                "window_ends": list(ends), "nan_chains": nan_chains}
+        if dense:
+            rep["metric_dense"] = self._M.cpu().numpy().copy()
         if ta is not None:
             rep.update(trajectory_length=float(self._T), T=T_hist, steps=steps_hist, nonfinite_chains=nonfinite)
         return rep

@@ -151,12 +151,19 @@ class _HMCKernel:
     adapt_metric (extension): before the moves of every temperature the dense metric is set to the particles' own
     per-coordinate variance (over all ranks) -- the scale of the tempered posterior shrinks by orders of magnitude
     along the ladder (config 5: prior width 1 -> posterior width 0.05), and a fixed metric either barely moves the
-    early particles or rejects every late proposal."""
+    early particles or rejects every late proposal.  adapt_metric="dense": the particles' full covariance instead
+    (diagnostics.RunningCovariance: bk_cov_accumulate on the fp64 matrix cores, summed over ranks), shrunk as
+    HMCDiag.warmup shrinks it, M = n/(n+5) * cov + 1e-3 * 5/(n+5) * I with n the particles of all ranks; its Cholesky
+    factor and inverse are formed on the host once per temperature."""
 
     def __init__(self, stepsize, steps, draws=1, metric_diag=None, metric_dense=None, adapt_metric=False):
         self.stepsize, self.steps, self.draws = float(stepsize), int(steps), int(draws)
         self.metric_diag, self.metric_dense = metric_diag, metric_dense
+        if isinstance(adapt_metric, str) and adapt_metric != "dense":
+            raise ValueError(f"hmc_kernel: adapt_metric must be True, False or 'dense', got {adapt_metric!r}")
         self.adapt_metric = bool(adapt_metric)
+        self.adapt_dense = adapt_metric == "dense"
+        self._cov = None
         self._hmc = None
         self._target = None
         self._ll = None
@@ -179,6 +186,19 @@ class _HMCKernel:
         var = (stats[D:2 * D] / cnt - mean * mean).clamp(min=1e-300) * (cnt / (cnt - 1.0).clamp(min=1.0))
         return var
 
+    def _particle_covariance(self, smc):
+        from .diagnostics import RunningCovariance
+
+        if self._cov is None:
+            self._cov = RunningCovariance(smc.D, smc._ops)
+        cov = self._cov
+        cov.reset()
+        cov.update(smc._theta_dc, layout="dc", group=smc._group)
+        S, s, n = cov._totals(smc._group)
+        M = n / (n + 5.0) * ((S - torch.outer(s, s) / n) / (n - 1.0))
+        M.diagonal().add_(1e-3 * 5.0 / (n + 5.0))
+        return M
+
     def move(self, smc, t: float) -> None:
         from .hmc import HMCDiag
 
@@ -193,7 +213,9 @@ class _HMCKernel:
                                 metric_dense=md, graph=False, ops=smc._ops,
                                 prefetch_rng=False if self.adapt_metric else None)
         h = self._hmc
-        if self.adapt_metric and h._M is not None:
+        if self.adapt_dense and h._M is not None:
+            h.set_metric_dense(self._particle_covariance(smc))
+        elif self.adapt_metric and h._M is not None:
             h.set_metric_dense(self._particle_variance(smc))   # (1-D: a diagonal metric, installed on the device)
         self._target.t = float(t)
         h._theta_dc.copy_(smc._theta_dc)
@@ -245,7 +267,7 @@ class _HMCKernel:
 
 
 def hmc_kernel(stepsize: float, steps: int, draws: int = 1, metric_diag=None, metric_dense=None,
-               adapt_metric: bool = False) -> _HMCKernel:
+               adapt_metric=False) -> _HMCKernel:
     return _HMCKernel(stepsize, steps, draws, metric_diag, metric_dense, adapt_metric)
 
 

@@ -776,6 +776,24 @@ int bk_gemm_chains(const double* A, int64_t lda, int64_t R, int64_t K, const dou
 int bk_gemm_chains_logistic(const double* A, int64_t lda, int64_t R, int64_t K, const double* X, int64_t ldx,
                             double* Y, int64_t ldy, int64_t C, const double* y_rows, void* stream);
 
+/* Shifted scatter matrix of the state on the same matrix cores (csrc/bk_cov.hip), in place:
+ *     S += (X - center 1^T)(X - center 1^T)^T      S: [D][lds], lds >= D
+ *     s += rowsum(X - center 1^T)                  s: [D]
+ * X: the engine's [D][ld] array of C chains, ld >= C; center: [D], or NULL = zeros, subtracted as the panels are
+ * loaded.  With a center near the mean, (S - s s^T / n) / (n - 1) over n accumulated columns is their covariance
+ * without cancellation (the dense-metric warmup, RunningCovariance).  The reduction runs over the chain index; only
+ * tile blocks on or below the diagonal are computed and every value is written to (i, j) and (j, i) from S's LOWER
+ * triangle: a symmetric S stays exactly symmetric (an asymmetric one takes its lower triangle).  The chains are split
+ * into bk_cov_k_chunk(D)-sized chunks, grouped into slabs that are summed in a fixed order through `work` (caller-owned,
+ * at least bk_cov_accumulate_work_elems(D, C) doubles): no atomics, the same bits for the same call; the grouping, and
+ * with it the last bits, depends on C.  D^2 C (1 + 128 / D) flop.  Non-finite entries of X poison their rows and columns.
+ * BK_E_ARG: a NULL X, S or s, C < 0, D < 0, ld < C, lds < D, a NULL or too small `work` (with C, D >= 1); decided before
+ * any HIP call.  C == 0 or D == 0: BK_OK, nothing launched. */
+int64_t bk_cov_k_chunk(int64_t D);
+int64_t bk_cov_accumulate_work_elems(int64_t D, int64_t C);
+int bk_cov_accumulate(const double* X, int64_t ld, int64_t C, int64_t D, const double* center, double* S, int64_t lds,
+                      double* s, double* work, int64_t work_elems, void* stream);
+
 /* Logistic regression target (BASELINE.json config 5; no reference oracle), between the two
  * GEMMs Z = X_data @ Theta and G = X_data^T @ R:
  *   bk_logistic_residual: Z[n*ldz + c] <- y[n] - sigmoid(z) in place, and
