@@ -14,6 +14,8 @@ import numpy as np
 import torch
 
 from . import _lib
+from .adapt import DualAveraging, shrink_estimate, warmup_windows
+from .diagnostics import RunningMoments, _gather_sum, pooled_variance_from_moments
 
 _M64 = (1 << 64) - 1
 
@@ -252,6 +254,40 @@ class ManyChainSampler:
         # the reference can only be given a D>1 metric by assigning _metric
         self._set_metric(m)
 
+    # -- the diagonal preconditioner (HMCDiag, MALA) ----------------------------------------------
+    _pd = None  # packed preconditioner [3, D] = {v, sqrt(v), 1/v} on the device (precond_diag)
+
+    def _pack_precond(self, v):
+        """Validate v and form {v, sqrt(v), 1/v} on the device, in place once the buffer exists (a captured hipGraph keeps
+        pointing at it).  -> whether this call allocated the buffer."""
+        vt = torch.as_tensor(v, dtype=torch.float64).reshape(-1)
+        if vt.shape[0] != self._dim:
+            raise ValueError(f"precond_diag has {vt.shape[0]} entries, model has {self._dim} dims")
+        vt = vt.to(self._ops.device).contiguous()
+        if not bool((torch.isfinite(vt) & (vt > 0.0)).all()):
+            raise ValueError("precond_diag must hold finite, positive variances")
+        first = self._pd is None
+        if first:
+            self._pd = torch.empty((3, self._dim), dtype=torch.float64, device=self._ops.device)
+        self._ops.precond_pack(vt, self._pd)  # (the library's own sqrt and 1/x: the same doubles on every device)
+        return first
+
+    @property
+    def precond_diag(self):
+        """The preconditioner's variances as a host array (None when not set)."""
+        return None if self._pd is None else self._pd[0].cpu().numpy().copy()
+
+    def _precond_extra(self):  # (what a checkpoint's `extra` carries as "precond_diag")
+        return None if self._pd is None else self._pd[0].cpu().clone()
+
+    def _precond_from_extra(self, extra):
+        """-> the variances a checkpoint carries, for the sampler to install; None from an older checkpoint (no such key:
+        nothing changes); a checkpoint written without a preconditioner is refused by a sampler that has one."""
+        pv = extra.get("precond_diag")
+        if pv is None and self._pd is not None and "precond_diag" in extra:
+            raise ValueError("checkpoint was written without precond_diag, this sampler has one")
+        return pv
+
     # -- views of the state -------------------------------------------------------------------
     @property
     def _theta(self):
@@ -264,8 +300,8 @@ class ManyChainSampler:
         return self._C
 
     def rng_state(self) -> np.ndarray:
-        """uint64 [RNG_WORDS, C] snapshot of the per-chain streams (numpy field order)."""
-        return self._rng_state.cpu().numpy().view(np.uint64)
+        """uint64 [RNG_WORDS, C] snapshot of the per-chain streams (numpy field order), at their logical position."""
+        return self._logical_rng().cpu().numpy().view(np.uint64)
 
     @property
     def _rng(self):
@@ -331,6 +367,80 @@ class ManyChainSampler:
 
     def _load_extra(self, extra):
         pass
+
+    # -- cross-chain warmup (HMCDiag, MALA) ----------------------------------------------------------
+    _STEP_SIZE = None          # name of the attribute that holds the step size warmup() tunes
+    _stat = _stat_work = None  # warmup(): where a draw leaves its acceptance statistic (bk_accept_stat); its scratch
+
+    def _check_warmup(self, draws, target_accept):
+        draws = int(draws)
+        if draws < 1:
+            raise ValueError(f"warmup: draws must be >= 1, got {draws}")
+        if not 0.0 < float(target_accept) < 1.0:
+            raise ValueError(f"warmup: target_accept must be inside (0, 1), got {target_accept}")
+        if not self._batched:
+            raise ValueError("warmup needs a batched device model (the statistics are taken across chains)")
+        return draws
+
+    def _diag_estimator(self, group):
+        """warmup()'s estimate of precond_diag: Welford moments of the state after every draw of a window (two [D, C]
+        arrays), pooled over all chains of all ranks and shrunk at its end."""
+        mom = RunningMoments(self._dim, self._C, self._ops)
+
+        def install(chains_total):
+            var = pooled_variance_from_moments(mom.mean, mom.m2, mom.n, self._ops, group)
+            self.set_precond_diag(shrink_estimate(var, float(mom.n) * chains_total))
+            mom.reset()
+
+        return (lambda: mom.update(self._theta_dc, layout="dc")), install
+
+    def _warmup_loop(self, draws, target_accept, group, draw, metric=None, observer=None):
+        """The warmup draws of HMCDiag and MALA -> the report (the common keys, then the observer's).  draw() launches one
+        draw, which leaves {sum of the statistic, NaN chains, chains} of this rank in `_stat`; metric: None (the step size
+        alone adapts) or metric(group) -> (update(), for a draw inside a window, install(chains_total), for a window's end);
+        observer: None or after_draw(totals of all ranks, the draw's step size, window_end, last) and report().  ONE host
+        read of one vector per draw, summed over ranks in rank order."""
+        C, dev = self._C, self._ops.device
+        init, term, ends = warmup_windows(draws)
+        if metric is None:
+            ends = []
+        da = DualAveraging(float(getattr(self, self._STEP_SIZE)), float(target_accept))
+        update, install = metric(group) if ends else (None, None)
+        # {sum of the statistic, NaN chains, chains} and, for an observer, two more of its own
+        self._stat = torch.zeros(3 if observer is None else 5, dtype=torch.float64, device=dev)
+        self._stat[2] = float(C)
+        self._stat_work = torch.empty(max(2, 2 * ((C + 255) // 256)), dtype=torch.float64, device=dev)
+        eps_hist, alpha_hist, nan_chains = [], [], 0
+        try:
+            for it in range(draws):
+                eps_hist.append(float(getattr(self, self._STEP_SIZE)))
+                draw()
+                self._draws += 1
+                tot = _gather_sum(self._stat, group).cpu()  # the warmup draw's one host read
+                chains_total = float(tot[2])
+                alpha = float(tot[0]) / chains_total
+                alpha_hist.append(alpha)
+                nan_chains += int(tot[1])
+                window_end, last = it + 1 in ends, it + 1 == draws
+                if update is not None and init <= it < draws - term:
+                    update()
+                eps = da.step(alpha)
+                if observer is not None:
+                    observer.after_draw(tot, eps_hist[-1], window_end, last)
+                if window_end:
+                    install(chains_total)
+                    eps = da.final()
+                    da.restart(eps)
+                if last:
+                    eps = da.final()
+                setattr(self, self._STEP_SIZE, eps)
+        finally:
+            self._stat = self._stat_work = None
+        rep = {"stepsize": float(getattr(self, self._STEP_SIZE)), "precond_diag": self.precond_diag, "eps": eps_hist,
+               "alpha": alpha_hist, "window_ends": list(ends), "nan_chains": nan_chains}
+        if observer is not None:
+            rep.update(observer.report())
+        return rep
 
     # -- hipGraph replay of a whole draw ----------------------------------------------------------
     # Small problems (e.g. 4096 chains x D=128: 4 MiB arrays) are launch-bound: ~2 L tiny

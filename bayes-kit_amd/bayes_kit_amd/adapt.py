@@ -1,5 +1,7 @@
-"""Host side of the cross-chain warmup (HMCDiag.warmup): the window schedule, the dual-averaging controller of the step
-size, and the jitter and the controller of the trajectory length.
+"""Host side of the cross-chain warmup (HMCDiag.warmup, MALA.warmup): the window schedule, the dual-averaging controller of
+the step size, the shrinkage of a window's estimate, and the jitter and the controller of the trajectory length.  The loop
+that drives them is ManyChainSampler._warmup_loop (_engine.py); a sampler supplies how a warmup draw is launched, where its
+step size lives, a metric estimator (update after a draw, install at a window's end) and, for ChEES, an observer of the totals.
 
 Pure Python on a handful of doubles per draw; everything that touches [D, C] arrays stays on the device
 (bk_accept_stat, bk_welford_update, bk_rhat_partials, bk_chees_sums, bk_chees_stat).  The window schedule's and dual
@@ -29,6 +31,18 @@ def warmup_windows(draws: int, init: int = 75, term: int = 50, base: int = 25):
         ends.append(end)
         start, w = end, 2 * w
     return init, term, ends
+
+
+def shrink_estimate(estimate, n_eff):
+    """A window's variances [D] or covariance [D, D] from n_eff points, shrunk towards 1e-3 times the unit metric (Stan's
+    regularisation): n/(n+5) * estimate + 1e-3 * 5/(n+5), for a matrix added to the diagonal (in place, of the product).
+    The order of the operations is part of the result: dual averaging amplifies one ulp of it to percents."""
+    shrunk = n_eff / (n_eff + 5.0) * estimate
+    floor = 1e-3 * 5.0 / (n_eff + 5.0)
+    if shrunk.ndim == 2:
+        shrunk.diagonal().add_(floor)
+        return shrunk
+    return shrunk + floor
 
 
 class DualAveraging:

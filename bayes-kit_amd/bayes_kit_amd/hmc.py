@@ -26,10 +26,37 @@ import torch
 
 from . import _lib
 from ._engine import ManyChainSampler
+from .adapt import TrajectoryAdam, jitter_steps, shrink_estimate
+from .diagnostics import RunningCovariance, _gather_sum
+
+
+class TrajectoryObserver:
+    """warmup(adapt_trajectory=True): feeds adapt.TrajectoryAdam with every draw's trajectory statistic (_stat[3:5]), assigns
+    the sampler's trajectory length for the next draw and keeps the report's histories."""
+
+    def __init__(self, sampler):
+        self._s, self._ta = sampler, TrajectoryAdam(sampler._T)
+        self._T_hist, self._steps_hist, self._nonfinite = [], [], 0
+
+    def after_draw(self, tot, eps, window_end, last):
+        s = self._s
+        self._T_hist.append(float(s._T))
+        self._steps_hist.append(int(s._steps))
+        self._nonfinite += int(tot[4])
+        s._T = self._ta.step(float(tot[3]), float(tot[0]), s._steps * eps, eps, s._max_steps)
+        if window_end:
+            self._ta.restart()  # (the geometry changes with the metric installed next)
+        if last:
+            s._T = self._ta.final()
+
+    def report(self):
+        return dict(trajectory_length=float(self._s._T), T=self._T_hist, steps=self._steps_hist,
+                    nonfinite_chains=self._nonfinite)
 
 
 class HMCDiag(ManyChainSampler):
     TUNING = ("graph", "prefetch_rng", "tune_placement", "chain_tile")
+    _STEP_SIZE = "_stepsize"
 
     def __init__(
         self,
@@ -81,9 +108,10 @@ class HMCDiag(ManyChainSampler):
         prefetch_rng, tune_placement = tn.get("prefetch_rng"), tn.get("tune_placement")
         self._stepsize = stepsize
         self._steps = steps
-        self._pd = None        # packed preconditioner [3, D] = {v, sqrt(v), 1/v} on the device (precond_diag)
-        self._stat = None      # warmup(): where a draw leaves its acceptance statistic (bk_accept_stat)
         self._chees = None     # warmup(adapt_trajectory=True): the scratch of the trajectory statistic (bk_chees_*)
+        # prefetch_rng (decided below): whether the NEXT draw's randomness has been generated ahead, the event that marks it
+        # complete (None: already joined), per slot the stream table before that slot's normals were generated
+        self._prefetch, self._pf_ready, self._pf_event, self._snap = False, False, None, None
         self._T, self._jitter_n, self._last_steps = None, 0, None
         self._max_steps = self._check_max_steps(max_steps)
         self._graph_explicit = graph is True
@@ -183,10 +211,7 @@ class HMCDiag(ManyChainSampler):
             prefetch_rng = self._batched and self._ops.device.type == "cuda"
         self._prefetch = bool(prefetch_rng) and self._batched and not self._use_graph
         self._pf_slot = 0           # double-buffer slot holding the NEXT draw's randomness
-        self._pf_ready = False      # ... once it has been generated
-        self._pf_event = None       # ... and the event that marks it complete (None: already joined)
         self._pf_kin_stale = False
-        self._snap = None           # per slot: the stream table before that slot's normals were generated
         if self._prefetch:
             if self._fused_zt:
                 self._zt_bufs.append(torch.empty_like(self._zt_bufs[0]))
@@ -237,43 +262,40 @@ class HMCDiag(ManyChainSampler):
         if self._M is None:
             raise ValueError("this sampler was built without metric_dense")
         self._install_metric_dense(metric_dense)
-        if self._prefetch and self._pf_ready:
-            if self._pf_event is not None:
-                torch.cuda.current_stream().wait_event(self._pf_event)
-            self._pf_ready, self._pf_event = False, None
-
-    def _rewind_prefetch(self):
-        """Drop randomness generated ahead (prefetch_rng) AND take the stream back to where its generation began, as
-        set_precond_diag does: the next draw generates it again, and the stream position stays that of a sampler
-        without prefetch_rng."""
-        if getattr(self, "_prefetch", False) and self._pf_ready:
-            if self._pf_event is not None:
-                torch.cuda.current_stream().wait_event(self._pf_event)
-            self._rng_state.copy_(self._rng_logical if self._snap is None else self._snap[self._pf_slot])
-            self._pf_ready, self._pf_event = False, None
+        self._drop_ahead(rewind=False)
 
     @property
     def metric_dense(self):
         """The dense metric as a host array (None when the sampler was built without one)."""
         return None if self._M is None else self._M.cpu().numpy().copy()
 
+    # -- randomness generated ahead: the two places that know where it leaves the stream ----------------------
+    def _stream_position(self):
+        """The tensor that holds the logical stream position (a sampler's without prefetch_rng): the table -- while the next
+        draw's randomness is generated ahead, the table as it was when that generation began, which is snap[slot], written
+        by the chain-major generator itself, or else _rng_logical, a copy queued in front of the generator."""
+        if self._prefetch and self._pf_ready:
+            return self._rng_logical if self._snap is None else self._snap[self._pf_slot]
+        return self._rng_state
+
+    def _drop_ahead(self, rewind):
+        """Between two draws: drop the randomness generated ahead, once its generator has finished (a GPU-side wait);
+        rewind: and take the stream back to where its generation began, for the next draw to generate it again."""
+        if self._prefetch and self._pf_ready:
+            if self._pf_event is not None:
+                torch.cuda.current_stream().wait_event(self._pf_event)
+            if rewind:
+                self._rng_state.copy_(self._stream_position())
+            self._pf_ready, self._pf_event = False, None
+
     # -- the proper diagonal preconditioner -----------------------------------------------------------
     def _install_precond(self, v):
-        """Validate v and form {v, sqrt(v), 1/v} on the device, in place once the buffer exists (a captured hipGraph
-        keeps pointing at it).  The kick kernels see the first row as their metric."""
+        """The preconditioner v, packed (_pack_precond); the kick kernels see its first row as their metric."""
         if self._M is not None or (self._pd is None and self._metric_dev is not None):
             raise ValueError("precond_diag cannot be combined with metric_diag / metric_dense")
-        vt = torch.as_tensor(v, dtype=torch.float64).reshape(-1)
-        if vt.shape[0] != self._dim:
-            raise ValueError(f"precond_diag has {vt.shape[0]} entries, model has {self._dim} dims")
-        vt = vt.to(self._ops.device).contiguous()
-        if not bool((torch.isfinite(vt) & (vt > 0.0)).all()):
-            raise ValueError("precond_diag must hold finite, positive variances")
-        if self._pd is None:
-            self._pd = torch.empty((3, self._dim), dtype=torch.float64, device=self._ops.device)
+        if self._pack_precond(v):
             self._metric_dev, self._metric_identity = self._pd[0], False
             self._drop_graphs()  # the captured launches had no preconditioner: capture again
-        self._ops.precond_pack(vt, self._pd)  # (the library's own sqrt and 1/x: the same doubles on every device)
 
     def set_precond_diag(self, v):
         """Set or replace the diagonal preconditioner between draws (see ``precond_diag``).  Changes no stream position:
@@ -283,33 +305,21 @@ class HMCDiag(ManyChainSampler):
         self._install_precond(v)
         if self._fused_draw and not hasattr(self._model, "bk_hmc_draw_precond"):
             self._leave_whole_draw()
-        if getattr(self, "_prefetch", False) and self._pf_ready and not self._fused_zt:
-            if self._pf_event is not None:
-                torch.cuda.current_stream().wait_event(self._pf_event)
-            self._rng_state.copy_(self._rng_logical)
-            self._pf_ready, self._pf_event = False, None
+        if not self._fused_zt:
+            self._drop_ahead(rewind=True)
 
     def _leave_whole_draw(self):
         """From the whole-draw kernel to the step-by-step path between two draws (a preconditioner was set on a model whose
         whole-draw hook has no preconditioned form): the stream goes back to where the next draw's randomness began, the
         momentum gets its state-layout buffers, and the cached gradient is evaluated again (the whole-draw path keeps the
         log density only; the same kernel gives the same value)."""
-        if self._prefetch and self._pf_ready:
-            if self._pf_event is not None:
-                torch.cuda.current_stream().wait_event(self._pf_event)
-            self._rng_state.copy_(self._snap[self._pf_slot] if self._snap is not None else self._rng_logical)
-            self._pf_ready, self._pf_event = False, None
+        self._drop_ahead(rewind=True)
         self._fused_draw = self._fused = self._fused_zt = False
         self._rho_bufs = [r if r is not None else torch.empty_like(self._thp_raw) for r in self._rho_bufs]
         if self._prefetch and self._snap is not None:
             self._snap, self._rng_logical = None, self._rng_state.clone()
         self._have_cache = False
         self._drop_graphs()
-
-    @property
-    def precond_diag(self):
-        """The preconditioner's variances as a host array (None when not set)."""
-        return None if self._pd is None else self._pd[0].cpu().numpy().copy()
 
     # -- a jittered trajectory length ------------------------------------------------------------------
     @staticmethod
@@ -366,8 +376,6 @@ class HMCDiag(ManyChainSampler):
     def _next_steps(self):
         """Assign ``steps`` for the draw about to run: L_n of the next jittered draw, or what it is."""
         if self._T is not None:
-            from .adapt import jitter_steps
-
             self._jitter_n += 1
             self._steps = jitter_steps(self._jitter_n, self._T, float(self._stepsize), self._max_steps)
         self._last_steps = int(self._steps)
@@ -376,11 +384,7 @@ class HMCDiag(ManyChainSampler):
         """The mirror of _leave_whole_draw, between two draws: the stream goes back to the logical position (a momentum
         generated ahead in the state layout is dropped), the chain-major normals and the stream snapshots come back, graphs
         are dropped.  The whole-draw kernel needs the current log density only, which the step-by-step path kept."""
-        if self._prefetch and self._pf_ready:
-            if self._pf_event is not None:
-                torch.cuda.current_stream().wait_event(self._pf_event)
-            self._rng_state.copy_(self._rng_logical if self._snap is None else self._snap[self._pf_slot])
-            self._pf_ready, self._pf_event = False, None
+        self._drop_ahead(rewind=True)
         D, C, dev = self._dim, self._C, self._ops.device
         self._fused_draw = self._fused = True
         self._fused_zt = self._rng_kind == _lib.RNG_PHILOX and D >= 32
@@ -570,31 +574,25 @@ class HMCDiag(ManyChainSampler):
         super()._set_metric(m)
         self._pf_kin_stale = True  # a prefetched kinetic energy was computed with the old metric
 
-
-    def rng_state(self):
-        return self._logical_rng().cpu().numpy().view(np.uint64)
-
     def _state_tensors(self):
         return {"theta": self._theta_dc, "grad": self._grad, "lp": self._lp, "accepted": self._accepted}
 
     def _logical_rng(self):
-        if getattr(self, "_prefetch", False) and self._pf_ready:
-            if self._pf_event is not None:
-                self._pf_event.synchronize()
-            return self._rng_logical if self._snap is None else self._snap[self._pf_slot]
-        return self._rng_state
+        if self._prefetch and self._pf_ready and self._pf_event is not None:
+            self._pf_event.synchronize()
+        return self._stream_position()
 
     def load_state_dict(self, sd):
-        if getattr(self, "_prefetch", False) and self._pf_ready:
+        if self._prefetch and self._pf_ready:
             torch.cuda.synchronize()  # (the generator queued ahead has finished before its bookkeeping goes)
-            self._pf_ready, self._pf_event = False, None
+        self._drop_ahead(rewind=False)
         if self._rebind:
             # the state array is the last draw handed out (see _draw): restore into a fresh one
             self._theta_dc = torch.empty_like(self._theta_dc)
         super().load_state_dict(sd)
 
     def _state_extra(self):
-        return {"stepsize": float(self._stepsize), "precond_diag": None if self._pd is None else self._pd[0].cpu().clone(),
+        return {"stepsize": float(self._stepsize), "precond_diag": self._precond_extra(),
                 "trajectory_length": self._T, "max_steps": self._max_steps, "jitter_n": self._jitter_n,
                 "metric_dense": None if self._M is None else self._M.cpu().clone()}
 
@@ -606,14 +604,9 @@ class HMCDiag(ManyChainSampler):
             self._max_steps = self._check_max_steps(extra["max_steps"])
             self.set_trajectory_length(extra["trajectory_length"])
             self._jitter_n = int(extra["jitter_n"])
-        pv = extra.get("precond_diag")
+        pv = self._precond_from_extra(extra)
         if pv is not None:
-            # (randomness generated ahead was dropped by load_state_dict: nothing here moves the restored stream)
-            self._install_precond(pv)
-            if self._fused_draw and not hasattr(self._model, "bk_hmc_draw_precond"):
-                self._leave_whole_draw()
-        elif self._pd is not None and "precond_diag" in extra:
-            raise ValueError("checkpoint was written without precond_diag, this sampler has one")
+            self.set_precond_diag(pv)  # (randomness generated ahead was dropped by load_state_dict: the stream stays put)
         Md = extra.get("metric_dense")  # (older checkpoints carry none: the sampler keeps what it was built with)
         if Md is not None:
             if self._M is None:
@@ -673,10 +666,8 @@ class HMCDiag(ManyChainSampler):
         return self._gp_raw
 
     # The side-stream generator (prefetch_rng) runs ONE draw ahead: at the start of draw n the generator
-    # of draw n+1 is queued.  `_pf_slot` is the slot the next draw consumes, and the stream position the
-    # reference's generator would have between two sample() calls is the table as it was when that
-    # slot's generation began: snap[slot], written by the chain-major generator itself, or else
-    # _rng_logical (a copy queued in front of the generator).
+    # of draw n+1 is queued.  `_pf_slot` is the slot the next draw consumes; _stream_position() is where the
+    # reference's generator would be between two sample() calls.
     # For the one-pass draw (bk_hmc_draw), which is fp64-VALU bound like the generator, two other
     # schedules were measured at 65,536 x 1024 on one box (tools/fused_hmc_profile_run.py): queueing the
     # generator of draw n+2 right after draw n's accept test, so that it starts under the HBM-bound
@@ -720,6 +711,18 @@ class HMCDiag(ManyChainSampler):
         return (float(self._stepsize), int(self._steps))
 
     # -- warmup -------------------------------------------------------------------------------------
+    def _dense_estimator(self, group):
+        """warmup(adapt_metric="dense")'s estimate of metric_dense: as _diag_estimator, with diagnostics.RunningCovariance."""
+        cov = RunningCovariance(self._dim, self._ops)
+
+        def install(chains_total):
+            Mn = shrink_estimate(cov.covariance(group), float(cov.n // self._C) * chains_total)
+            self._drop_ahead(rewind=True)  # (the momentum generated ahead carries the old metric: generate it again)
+            self.set_metric_dense(Mn)
+            cov.reset()
+
+        return (lambda: cov.update(self._theta_dc, layout="dc", group=group)), install
+
     def warmup(self, draws, target_accept=0.8, adapt_metric=True, group=None, *, adapt_trajectory=False, max_steps=None):
         """Run `draws` draws that tune the step size and (adapt_metric) the diagonal preconditioner from ALL chains of all
         ranks, then keep the tuned values: afterwards the sampler samples with them.  -> report dict: ``stepsize``,
@@ -773,14 +776,6 @@ class HMCDiag(ManyChainSampler):
         contraction (after a restart it swings the step size across the stability limit and back), so that rounding grows: two
         world sizes end at different, equally valid adaptations (observed: eps 0.647 against 0.675, v within 3 % of each
         other and of the truth)."""
-        from .adapt import DualAveraging, TrajectoryAdam, warmup_windows
-        from .diagnostics import RunningCovariance, RunningMoments, _gather_sum, pooled_variance_from_moments
-
-        draws = int(draws)
-        if draws < 1:
-            raise ValueError(f"warmup: draws must be >= 1, got {draws}")
-        if not 0.0 < float(target_accept) < 1.0:
-            raise ValueError(f"warmup: target_accept must be inside (0, 1), got {target_accept}")
         dense = isinstance(adapt_metric, str)
         if dense:
             if adapt_metric != "dense":
@@ -804,91 +799,36 @@ class HMCDiag(ManyChainSampler):
                 max_steps = self._check_max_steps(max_steps)
         elif max_steps is not None:
             raise ValueError("warmup: max_steps bounds the adapted trajectory, pass it with adapt_trajectory=True")
-        if not self._batched:
-            raise ValueError("warmup needs a batched device model (the statistics are taken across chains)")
-        ops, dev, C, D = self._ops, self._ops.device, self._C, self._dim
-        init, term, ends = warmup_windows(draws)
-        if not adapt_metric:
-            ends = []
-        da = DualAveraging(float(self._stepsize), float(target_accept))
-        mom = RunningMoments(D, C, ops) if (ends and not dense) else None
-        cov = RunningCovariance(D, ops) if (ends and dense) else None
-        # {sum of the statistic, NaN chains, chains} and, adapting the trajectory, {sum of w g, chains with a non-finite g}
-        self._stat = torch.zeros(5 if adapt_trajectory else 3, dtype=torch.float64, device=dev)
-        self._stat[2] = float(C)
-        self._stat_work = torch.empty(max(2, 2 * ((C + 255) // 256)), dtype=torch.float64, device=dev)
-        eps_hist, alpha_hist, nan_chains = [], [], 0
-        ta, was_fused, T_hist, steps_hist, nonfinite = None, False, [], [], 0
+        draws = self._check_warmup(draws, target_accept)
+        observer, was_fused = None, False
         if adapt_trajectory:
+            ops, dev, C, D = self._ops, self._ops.device, self._C, self._dim
             if max_steps is not None:
                 self._max_steps = max_steps
             self.set_trajectory_length(self._T if self._T is not None else float(self._steps) * float(self._stepsize))
-            ta = TrajectoryAdam(self._T)
+            observer = TrajectoryObserver(self)
             was_fused = self._fused_draw
             if was_fused:
                 self._leave_whole_draw()
             sums = torch.zeros(2 * D + 1, dtype=torch.float64, device=dev)  # {sum theta, sum theta', chains}
             sums[2 * D] = float(C)
             self._chees = (sums, torch.empty(ops.chees_work_elems(C), dtype=torch.float64, device=dev), group)
+
+        def draw():
+            self._next_steps()
+            self._draw()
+            self._join_side_stream()
+
+        metric = (self._dense_estimator if dense else self._diag_estimator) if adapt_metric else None
         try:
-            for it in range(draws):
-                eps_hist.append(float(self._stepsize))
-                self._next_steps()
-                if ta is not None:
-                    T_hist.append(float(self._T))
-                    steps_hist.append(int(self._steps))
-                self._draw()
-                self._join_side_stream()
-                self._draws += 1
-                tot = _gather_sum(self._stat, group).cpu()  # the warmup draw's one host read
-                chains_total = float(tot[2])
-                alpha = float(tot[0]) / chains_total
-                alpha_hist.append(alpha)
-                nan_chains += int(tot[1])
-                if mom is not None and init <= it < draws - term:
-                    mom.update(self._theta_dc, layout="dc")
-                if cov is not None and init <= it < draws - term:
-                    cov.update(self._theta_dc, layout="dc", group=group)
-                eps = da.step(alpha)
-                if ta is not None:
-                    nonfinite += int(tot[4])
-                    self._T = ta.step(float(tot[3]), float(tot[0]), self._steps * eps_hist[-1], eps_hist[-1],
-                                      self._max_steps)
-                    if it + 1 in ends:
-                        ta.restart()  # (the geometry changes with the metric below)
-                    if it + 1 == draws:
-                        self._T = ta.final()
-                if it + 1 in ends and cov is not None:
-                    n_eff = float(cov.n // C) * chains_total
-                    Mn = n_eff / (n_eff + 5.0) * cov.covariance(group)
-                    Mn.diagonal().add_(1e-3 * 5.0 / (n_eff + 5.0))
-                    self._rewind_prefetch()  # (the momentum generated ahead carries the old metric: generate it again)
-                    self.set_metric_dense(Mn)
-                    cov.reset()
-                    eps = da.final()
-                    da.restart(eps)
-                elif it + 1 in ends:
-                    n_eff = float(mom.n) * chains_total
-                    var = pooled_variance_from_moments(mom.mean, mom.m2, mom.n, ops, group)
-                    self.set_precond_diag(n_eff / (n_eff + 5.0) * var + 1e-3 * 5.0 / (n_eff + 5.0))
-                    mom.reset()
-                    eps = da.final()
-                    da.restart(eps)
-                if it + 1 == draws:
-                    eps = da.final()
-                self._stepsize = eps
+            rep = self._warmup_loop(draws, target_accept, group, draw, metric, observer)
         finally:
-            self._stat, self._stat_work, self._chees, self._rho_cur = None, None, None, None
-            del mom, cov
+            self._chees, self._rho_cur = None, None
             self._drop_graphs()
             if was_fused and (self._pd is None or hasattr(self._model, "bk_hmc_draw_precond")):
                 self._enter_whole_draw()
-        rep = {"stepsize": float(self._stepsize), "precond_diag": self.precond_diag, "eps": eps_hist, "alpha": alpha_hist,
-               "window_ends": list(ends), "nan_chains": nan_chains}
         if dense:
             rep["metric_dense"] = self._M.cpu().numpy().copy()
-        if ta is not None:
-            rep.update(trajectory_length=float(self._T), T=T_hist, steps=steps_hist, nonfinite_chains=nonfinite)
         return rep
 
     # -- one draw for every chain ------------------------------------------------------------------
@@ -1036,8 +976,6 @@ class HMCDiag(ManyChainSampler):
         """The trajectory statistic of this draw into _stat[3:5] (state, log density and proposal are still intact): sums
         over this rank's chains, all ranks' sums in rank order, the means (divided by the chain count as a TENSOR: the same
         doubles on every device, see diagnostics._cross_chain_moments), then the weighted gradient."""
-        from .diagnostics import _gather_sum
-
         ops, D = self._ops, self._dim
         sums, work, group = self._chees
         ops.chees_sums(self._theta_dc, self._thp_raw, sums)

@@ -47,6 +47,7 @@ class MALA(ManyChainSampler):
     SINGLE_LAUNCH_MAX_DIMS = 4096  # (one lane walks the coordinates: the single-chain mode is for small models)
 
     TUNING = ("graph", "prefetch_rng", "tune_placement", "two_pass", "single_launch")
+    _STEP_SIZE = "_epsilon"
 
     def __init__(self, model, epsilon: float, init=None, seed=None, *, chains: Optional[int] = None,
                  chain_id0: int = 0, path: str = "auto", precond_diag=None, tuning: Optional[dict] = None, ops=None,
@@ -67,9 +68,9 @@ class MALA(ManyChainSampler):
         graph, prefetch_rng, tune_placement = tn.get("graph"), tn.get("prefetch_rng"), tn.get("tune_placement")
         two_pass, single_launch = tn.get("two_pass"), tn.get("single_launch")
         self._epsilon = epsilon
-        self._pd = None        # packed preconditioner [3, D] = {v, sqrt(v), 1/v} on the device (precond_diag)
         self._setup(model, None, init, seed, chains, chain_id0, ops)
-        pv = None if precond_diag is None else self._check_precond(precond_diag)
+        if precond_diag is not None:
+            self._pack_precond(precond_diag)
         self._init_graph(graph, prefetch_rng)
         D, C, dev = self._dim, self._C, self._ops.device
         f64 = dict(dtype=torch.float64, device=dev)
@@ -111,8 +112,6 @@ class MALA(ManyChainSampler):
                              and hasattr(model, "bk_eval"))
         self._sep_step = False
         self._grad_stale = False
-        if pv is not None:
-            self._pack_precond(pv)
         self._route()
         nbuf = 2 if self._prefetch else 1
         if self._chain_major:
@@ -161,23 +160,11 @@ class MALA(ManyChainSampler):
         self._materialize(self._eval_grad(self._theta_dc, self._grad, self._lp), self._grad)
 
     # -- the diagonal preconditioner ------------------------------------------------------------------------------
-    def _check_precond(self, v):
+    def _pack_precond(self, v):
         if not self._batched:
             raise ValueError("precond_diag needs a batched device model (the one-launch single-chain mode is not "
                              "preconditioned)")
-        vt = torch.as_tensor(v, dtype=torch.float64).reshape(-1)
-        if vt.shape[0] != self._dim:
-            raise ValueError(f"precond_diag has {vt.shape[0]} entries, model has {self._dim} dims")
-        vt = vt.to(self._ops.device).contiguous()
-        if not bool((torch.isfinite(vt) & (vt > 0.0)).all()):
-            raise ValueError("precond_diag must hold finite, positive variances")
-        return vt
-
-    def _pack_precond(self, vt):
-        """{v, sqrt(v), 1/v} on the device, in place once the buffer exists."""
-        if self._pd is None:
-            self._pd = torch.empty((3, self._dim), dtype=torch.float64, device=self._ops.device)
-        self._ops.precond_pack(vt, self._pd)  # (the library's own sqrt and 1/x: the same doubles on every device)
+        return super()._pack_precond(v)
 
     def _route(self):
         """Which step kernel a two-pass draw uses, and `path`."""
@@ -202,15 +189,9 @@ class MALA(ManyChainSampler):
         """Set or replace the diagonal preconditioner between draws (see ``precond_diag``).  Changes no logical stream
         position: a proposal made ahead with the old v is discarded and its normals are drawn again, same values (as
         ``refresh_cache``); captured graphs are dropped."""
-        vt = self._check_precond(v)
+        self._pack_precond(v)
         self._invalidate_pipe(restore_stream=True)
-        self._pack_precond(vt)
         self._route()
-
-    @property
-    def precond_diag(self):
-        """The preconditioner's variances as a host array (None when not set)."""
-        return None if self._pd is None else self._pd[0].cpu().numpy().copy()
 
     def _propose(self, th, g, z, thp, eps):
         """theta' from drawn normals z (either layout) [mala.py:41-45]."""
@@ -248,6 +229,13 @@ class MALA(ManyChainSampler):
         self._invalidate_pipe(restore_stream=True)
         self._materialize(self._eval_grad(self._theta_dc, self._grad, self._lp), self._grad)
         self._grad_stale = False
+
+    def _drop_ahead(self):
+        """Step by step with prefetch_rng, between two draws: drop the randomness generated ahead and take the stream back to
+        where that began (the draw that queued the generator has joined it: _join_side_stream)."""
+        if self._prefetch and self._pf_ready:
+            self._rng_state.copy_(self._rng_logical)
+        self._pf_ready, self._pf_event = False, None
 
     def _invalidate_pipe(self, restore_stream):
         if (self._two_pass or getattr(self, "_single", False)) and self._pipe_valid and restore_stream:
@@ -299,9 +287,6 @@ class MALA(ManyChainSampler):
             return self._rng_logical
         return self._rng_state
 
-    def rng_state(self):
-        return self._logical_rng().cpu().numpy().view(np.uint64)
-
     def load_state_dict(self, sd):
         if self._two_pass:
             # draws handed out earlier alias past state arrays: restore into a fresh one
@@ -309,19 +294,17 @@ class MALA(ManyChainSampler):
         super().load_state_dict(sd)
 
     def _state_extra(self):
-        return {"epsilon": float(self._epsilon), "precond_diag": None if self._pd is None else self._pd[0].cpu().clone()}
+        return {"epsilon": float(self._epsilon), "precond_diag": self._precond_extra()}
 
     def _load_extra(self, extra):
         # (checkpoints written before the step size and the preconditioner were carried hold neither: nothing changes)
         if "epsilon" in extra:
             self._epsilon = extra["epsilon"]
-        pv = extra.get("precond_diag")
+        pv = self._precond_from_extra(extra)
         if pv is not None:
-            self._pack_precond(self._check_precond(pv))
+            self._pack_precond(pv)
             self._grad_stale = False  # (the gradient of the restored point came with it)
             self._route()
-        elif self._pd is not None and "precond_diag" in extra:
-            raise ValueError("checkpoint was written without precond_diag, this sampler has one")
 
     def _after_load(self):
         self._grad_stale = False  # (the gradient of the restored point came with it)
@@ -553,7 +536,7 @@ class MALA(ManyChainSampler):
         self._select(self._mask, th, thp, self._grad, gp)
 
     # -- warmup -------------------------------------------------------------------------------------
-    def _warmup_draw(self, stat, work, zero, ratio):
+    def _warmup_draw(self, zero, ratio):
         """One draw as the step-by-step composition, whatever the sampler's own path: generator, proposal from the drawn
         normals, the model's gradient op, proposal densities, the acceptance statistic, accept, select."""
         ops = self._ops
@@ -573,7 +556,7 @@ class MALA(ManyChainSampler):
         torch.sub(self._lp_p, self._lp, out=ratio)
         torch.sub(self._rev, self._fwd, out=self._ret)
         ratio.add_(self._ret)
-        ops.accept_stat(zero, None, ratio, None, stat, work)
+        ops.accept_stat(zero, None, ratio, None, self._stat, self._stat_work)
         ops.mh_accept(_lib.ACCEPT_MALA, self._lp, self._fwd, self._lp_p, self._rev, logu,
                       self._mask, self._ret, self._accepted)
         self._select(self._mask, th, thp, self._grad, gp)
@@ -594,67 +577,21 @@ class MALA(ManyChainSampler):
         sequence makes the report identical bit for bit whatever ``two_pass``, ``path``, ``prefetch_rng`` and ``graph`` say.
         A proposal made ahead before the call is discarded (its normals are drawn again); afterwards graphs are dropped
         and the next ``sample()`` makes its proposal with the final epsilon and v."""
-        from .adapt import DualAveraging, warmup_windows
-        from .diagnostics import RunningMoments, _gather_sum, pooled_variance_from_moments
-
-        draws = int(draws)
-        if draws < 1:
-            raise ValueError(f"warmup: draws must be >= 1, got {draws}")
-        if not 0.0 < float(target_accept) < 1.0:
-            raise ValueError(f"warmup: target_accept must be inside (0, 1), got {target_accept}")
-        if not self._batched:
-            raise ValueError("warmup needs a batched device model (the statistics are taken across chains)")
-        ops, dev, C, D = self._ops, self._ops.device, self._C, self._dim
-        init, term, ends = warmup_windows(draws)
-        if not adapt_metric:
-            ends = []
-        # pipeline off: back to the logical stream position, nothing made ahead
+        draws = self._check_warmup(draws, target_accept)
+        # pipeline off: back to the logical stream position, nothing made or generated ahead
         self._invalidate_pipe(restore_stream=True)
-        if self._prefetch and self._pf_ready:  # (step by step: the next draw's randomness was generated ahead)
-            if self._pf_event is not None:
-                torch.cuda.current_stream().wait_event(self._pf_event)
-            self._rng_state.copy_(self._rng_logical)
-        self._pf_ready, self._pf_event = False, None
+        self._drop_ahead()
         self._fresh_grad()
         if self._two_pass and not self._use_graph:
             # (the state array is the last draw handed out: the in-place select below must not write into it)
             keep = self._theta_dc
             self._theta_dc = self._new_state()
             self._theta_dc.copy_(keep)
-        da = DualAveraging(float(self._epsilon), float(target_accept))
-        mom = RunningMoments(D, C, ops) if ends else None
-        f64 = dict(dtype=torch.float64, device=dev)
-        stat = torch.zeros(3, **f64)  # {sum of the statistic, NaN chains, chains}
-        stat[2] = float(C)
-        work = torch.empty(max(2, 2 * ((C + 255) // 256)), **f64)
-        zero, ratio = torch.zeros(C, **f64), torch.empty(C, **f64)
-        eps_hist, alpha_hist, nan_chains = [], [], 0
+        f64 = dict(dtype=torch.float64, device=self._ops.device)
+        zero, ratio = torch.zeros(self._C, **f64), torch.empty(self._C, **f64)
         try:
-            for it in range(draws):
-                eps_hist.append(float(self._epsilon))
-                self._warmup_draw(stat, work, zero, ratio)
-                self._draws += 1
-                tot = _gather_sum(stat, group).cpu()  # the warmup draw's one host read
-                chains_total = float(tot[2])
-                alpha = float(tot[0]) / chains_total
-                alpha_hist.append(alpha)
-                nan_chains += int(tot[1])
-                if mom is not None and init <= it < draws - term:
-                    mom.update(self._theta_dc, layout="dc")
-                eps = da.step(alpha)
-                if it + 1 in ends:
-                    n_eff = float(mom.n) * chains_total
-                    var = pooled_variance_from_moments(mom.mean, mom.m2, mom.n, ops, group)
-                    self.set_precond_diag(n_eff / (n_eff + 5.0) * var + 1e-3 * 5.0 / (n_eff + 5.0))
-                    mom.reset()
-                    eps = da.final()
-                    da.restart(eps)
-                if it + 1 == draws:
-                    eps = da.final()
-                self._epsilon = eps
+            return self._warmup_loop(draws, target_accept, group, lambda: self._warmup_draw(zero, ratio),
+                                     self._diag_estimator if adapt_metric else None)
         finally:
-            del mom
             self._grad_stale = False  # (the select above kept the stored gradient current)
             self._invalidate_pipe(restore_stream=False)
-        return {"stepsize": float(self._epsilon), "precond_diag": self.precond_diag, "eps": eps_hist, "alpha": alpha_hist,
-                "window_ends": list(ends), "nan_chains": nan_chains}

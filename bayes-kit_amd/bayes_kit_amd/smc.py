@@ -187,6 +187,7 @@ class _HMCKernel:
         return var
 
     def _particle_covariance(self, smc):
+        from .adapt import shrink_estimate
         from .diagnostics import RunningCovariance
 
         if self._cov is None:
@@ -195,9 +196,7 @@ class _HMCKernel:
         cov.reset()
         cov.update(smc._theta_dc, layout="dc", group=smc._group)
         S, s, n = cov._totals(smc._group)
-        M = n / (n + 5.0) * ((S - torch.outer(s, s) / n) / (n - 1.0))
-        M.diagonal().add_(1e-3 * 5.0 / (n + 5.0))
-        return M
+        return shrink_estimate((S - torch.outer(s, s) / n) / (n - 1.0), n)
 
     def move(self, smc, t: float) -> None:
         from .hmc import HMCDiag

@@ -1,6 +1,10 @@
 """Checks of the diagonal preconditioner (HMCDiag(precond_diag=v)), the adaptation statistics and HMCDiag.warmup that
 take the kernel library as an argument: tests/test_adapt_cpu.py runs them on the NumPy stand-in (tests/fake_ops_adapt.py),
 tests/test_gpu_adapt.py on the HIP library."""
+import hashlib
+import json
+import os
+
 import numpy as np
 import torch
 
@@ -174,3 +178,58 @@ def check_warmup_report(rep, lam, draws=300):
 def reports_equal(a, b):
     return (a["stepsize"] == b["stepsize"] and np.array_equal(a["precond_diag"], b["precond_diag"]) and a["eps"] == b["eps"]
             and a["alpha"] == b["alpha"] and a["window_ends"] == b["window_ends"] and a["nan_chains"] == b["nan_chains"])
+
+
+# ---- the stand-ins' warmups, recorded ----------------------------------------------------------------------------------
+# Six small warmups of HMCDiag on the NumPy stand-ins (96 chains; every branch of the warmup loop: the diagonal and the dense
+# estimator, none, no window at all, the trajectory controller alone and with windows), recorded in
+# tests/golden/hmc_warmup_standin.json: tests/test_adapt_cpu.py checks that the stand-ins still produce exactly them.
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "hmc_warmup_standin.json")
+WARMUP_CASES = ("diag", "stepsize_only", "no_window", "dense", "chees", "chees_windows")
+
+
+def _warmup_case(name):
+    """-> (sampler, warmup draws, warmup keywords); 60 draws have one window, ending after draw 54."""
+    from tests import dense_adapt_parity as dp
+    from tests.fake_ops_adapt import AdaptFakeOps
+    from tests.fake_ops_chees import CheesFakeOps
+    from tests.fake_ops_dense_adapt import DenseAdaptFakeOps
+
+    if name == "dense":  # (the correlated target of tests/dense_adapt_parity.py at D = 6)
+        return dp.make_sampler(DenseAdaptFakeOps(), 13, D=6, C=96), 60, dict(adapt_metric="dense")
+    ops = CheesFakeOps() if name.startswith("chees") else AdaptFakeOps()
+    s = bk.HMCDiag(bk.DiagGaussian(np.logspace(0, 3, 8), ops=ops), 0.006, 16, chains=96, seed=13, ops=ops)
+    draws, kw = {"diag": (60, dict()), "stepsize_only": (60, dict(adapt_metric=False)), "no_window": (15, dict()),
+                 "chees": (60, dict(adapt_metric=False, adapt_trajectory=True)),
+                 "chees_windows": (60, dict(adapt_trajectory=True))}[name]
+    return s, draws, kw
+
+
+def _jsonable(x):
+    if isinstance(x, np.ndarray):
+        return [_jsonable(y) for y in x.tolist()]
+    if isinstance(x, (list, tuple)):
+        return [_jsonable(y) for y in x]
+    return x.item() if isinstance(x, np.generic) else x
+
+
+def warmup_record(name):
+    """The warmup of one case -> a JSON-able record: the whole report (doubles survive repr exactly), theta and logp of the
+    two draws that follow and the stream table after them as digests of their bytes."""
+    s, draws, kw = _warmup_case(name)
+    rec = {k: _jsonable(v) for k, v in s.warmup(draws, **kw).items()}
+    sha = lambda a: hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()  # noqa: E731
+    th, lp = run_draws(s, 2)
+    rec.update(after_theta_sha256=sha(th), after_logp_sha256=sha(lp), rng_state_sha256=sha(s.rng_state()))
+    return rec
+
+
+def golden_record(name):
+    with open(GOLDEN) as f:
+        return json.load(f)[name]
+
+
+if __name__ == "__main__":  # PYTHONPATH=.:bayes-kit_amd python -m tests.adapt_parity: write the golden file from the stand-ins
+    with open(GOLDEN, "w") as f:
+        json.dump({name: warmup_record(name) for name in WARMUP_CASES}, f, indent=0)
+        f.write("\n")

@@ -227,6 +227,15 @@ def test_warmup_step_size_only():
     assert rep2["precond_diag"] is None and rep2["eps"] == rep["eps"]
 
 
+@pytest.mark.parametrize("case", ap.WARMUP_CASES)
+def test_warmup_is_the_recorded_run(case):
+    """Every kind of warmup on the stand-ins against its record (tests/golden/hmc_warmup_standin.json): the whole report,
+    its keys in their order, the two draws that follow and the stream position after them, all with ==."""
+    rec, want = ap.warmup_record(case), ap.golden_record(case)
+    assert list(rec) == list(want)
+    assert rec == want
+
+
 # ---- refusals -------------------------------------------------------------------------------------------------------
 def test_refusals_name_the_argument():
     ops = AdaptFakeOps()
