@@ -10,6 +10,7 @@ from . import _lib  # noqa: F401
 from . import dist  # noqa: F401
 from .diagnostics import DrawRecorder, DrawStore, RunningCovariance, RunningMoments, rhat_from_moments
 from .diagnostics import ess_bulk, ess_mean, ess_quantile, ess_tail, mcse_mean
+from .diagnostics import nested_rhat, nested_rhat_from_moments, superchain_init
 # like the reference (bayes_kit/__init__.py:2-13) the function names shadow the sub-modules of
 # the same name; importing them through the sub-modules keeps `bayes_kit_amd.rhat` a function
 # even after `from bayes_kit_amd.rhat import ...`
@@ -53,6 +54,9 @@ __all__ = [
     "DrawRecorder",
     "DrawStore",
     "rhat_from_moments",
+    "nested_rhat",
+    "nested_rhat_from_moments",
+    "superchain_init",
     "IsoGaussian",
     "DiagGaussian",
     "Funnel",

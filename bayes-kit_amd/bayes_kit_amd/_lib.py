@@ -106,6 +106,7 @@ SIGNATURES = {
     "bk_record_series_dev": [P, I, P, I, P, P, I, P, I, I, P],
     "bk_welford_update_dev": [P, P, I, P, I, P, I, I, I, P],
     "bk_rhat_partials": [P, P, I, I, P, P, I, I, P],
+    "bk_superchain_moments": [P, P, I, I, I, P, P, I, I, I, P],
     "bk_accept_stat": [P, P, P, P, I, P, P, P],
     "bk_chees_sums": [P, I, P, I, P, I, I, P],
     "bk_chees_stat": [P, I, P, I, P, I, P, P, P, P, P, P, P, I, I, P],
@@ -937,6 +938,15 @@ class Ops:
         D, C = mean.shape
         assert _ld(m2) == _ld(mean)
         self._call("bk_rhat_partials", ptr(mean), ptr(m2), _ld(mean), n, ptr(center), ptr(out), C, D,
+                   self._s())
+
+    def superchain_moments(self, mean, m2, n, M, s_out, w_out):
+        """s_out, w_out [D, C // M]: mean and Bt + Wt of every superchain of M consecutive chains (bk_superchain_moments);
+        m2 may be None for n = 1."""
+        D, C = mean.shape
+        assert m2 is None or _ld(m2) == _ld(mean)
+        assert _ld(w_out) == _ld(s_out) and tuple(s_out.shape) == tuple(w_out.shape) == (D, C // M)
+        self._call("bk_superchain_moments", ptr(mean), ptr(m2), _ld(mean), n, M, ptr(s_out), ptr(w_out), _ld(s_out), C, D,
                    self._s())
 
     def chain_mean_var(self, x, lengths, mean, var):

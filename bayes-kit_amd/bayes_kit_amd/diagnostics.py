@@ -85,6 +85,123 @@ def pooled_variance_from_moments(mean_dc, m2_dc, n: int, ops=None, group=None) -
     return (nf - 1.0) / nf * mean_var + var_means
 
 
+# ---------------------------------------------------------------------------------------------
+# nested R-hat: many short chains
+# ---------------------------------------------------------------------------------------------
+# Margossian, Hoffman, Sountsov, Riou-Durand, Vehtari, Gelman: "Nested R-hat: assessing the convergence of Markov chain
+# Monte Carlo when running many short chains".  The C chains are K superchains of M: chain c belongs to superchain c // M
+# (contiguous blocks, as dist.shard's), the M chains of a superchain share a start and differ by their streams.  Per
+# coordinate, with mu_km / M2_km the mean and Welford M2 of the n draws of chain k M + m:
+#     s_k  = mean_m(mu_km)
+#     Bt_k = sum_m (mu_km - s_k)^2 / (M - 1)      (0 for M = 1)
+#     Wt_k = mean_m(M2_km / (n - 1))              (0 for n = 1)
+#     B = var_k(s_k, ddof=1)       W = mean_k(Bt_k + Wt_k)       nested R-hat = sqrt(1 + B / W)
+# It is defined from the first draw on (n = 1 needs M >= 2) and its threshold tightens with M, not with n.  For M = 1,
+# nested R-hat^2 = R-hat^2 + 1/n.  NaN draws and W = 0 are not filtered: the result is what IEEE arithmetic gives (NaN, or
+# inf for B > 0 = W).
+#
+# The device reduces per superchain (bk_superchain_moments: s_k and Bt_k + Wt_k, [D, K]); across superchains
+# _cross_chain_moments already is mean_k / var_k over all ranks -- handed (s, w) as (mean, M2) with n = 2, its division by
+# n - 1 is a division by 1.0.  A superchain must not straddle ranks: every rank's chain count is a multiple of M.  So that
+# a rank which breaks this rule raises on EVERY rank inside the same two all_gathers, the arrays carry one more row: its
+# w is 1.0 on such a rank (which then contributes one dummy superchain) and 0.0 elsewhere, and a positive mean says so.
+def _check_superchain_args(n: int, M: int) -> None:
+    if M < 1:
+        raise ValueError(f"nested_rhat requires chains_per_superchain >= 1, but chains_per_superchain = {M}")
+    if n < 1:
+        raise ValueError("nested_rhat requires len(chain) >= 1 for every chain in chains")
+    if M == 1 and n == 1:
+        raise ValueError("nested_rhat requires chains_per_superchain >= 2 or len(chain) >= 2, but both are 1")
+
+
+def nested_rhat_from_moments(mean_dc, m2_dc, n: int, chains_per_superchain: int, ops=None, group=None) -> np.ndarray:
+    """Per-dimension nested R-hat from per-chain Welford moments ``mean, M2`` ([D, C_local] each, n draws per chain;
+    ``m2_dc`` may be None for n = 1), over ALL ranks' superchains of ``chains_per_superchain`` consecutive chains."""
+    ops = _ops(ops)
+    n, M = int(n), int(chains_per_superchain)
+    _check_superchain_args(n, M)
+    D, C = mean_dc.shape
+    dev = mean_dc.device
+    straddles = C % M != 0
+    multi = _bkdist.collectives_active(group)
+    if straddles and not multi:
+        raise ValueError(f"nested_rhat requires len(chains) to be a multiple of chains_per_superchain = {M}, "
+                         f"but len(chains) = {C}")
+    K = 1 if straddles else C // M
+    if straddles:
+        s = torch.zeros((D + 1, K), dtype=torch.float64, device=dev)
+        w = torch.zeros((D + 1, K), dtype=torch.float64, device=dev)
+        w[D] = 1.0
+    else:  # (the kernel writes every cell of the first D rows: only the flag row is cleared)
+        s = torch.empty((D + 1, K), dtype=torch.float64, device=dev)
+        w = torch.empty((D + 1, K), dtype=torch.float64, device=dev)
+        s[D].zero_()
+        w[D].zero_()
+        ops.superchain_moments(mean_dc, m2_dc if n > 1 else None, n, M, s[:D], w[:D])
+    try:
+        mean_w, var_s = _cross_chain_moments(s, w, 2, ops, group)
+    except ValueError as e:  # (its message counts chains; here they are superchains)
+        ours = f"nested_rhat requires len(chains) // {M} >= 2 superchains, but len(chains) // {M}"
+        raise ValueError(str(e).replace("rhat requires len(chains) >= 2, but len(chains)", ours)) from None
+    if multi and float(mean_w[D].item()) > 0.0:
+        raise ValueError(f"nested_rhat requires len(chains) to be a multiple of chains_per_superchain = {M} on every rank "
+                         "(a superchain must not straddle ranks)")
+    return torch.sqrt(1.0 + var_s[:D] / mean_w[:D]).cpu().numpy()
+
+
+def _nested_rhat_of_series(series, M: int, ops, group=None) -> np.ndarray:
+    """nested R-hat of each stored [n, C] series (chains in columns): per-chain moments by bk_chain_mean_var, M2 = var (n - 1)."""
+    if not series:
+        return np.empty(0)
+    n, C = series[0].shape
+    _check_superchain_args(int(n), int(M))
+    dev = series[0].device
+    mean = torch.empty((len(series), C), dtype=torch.float64, device=dev)
+    var = torch.empty((len(series), C), dtype=torch.float64, device=dev) if n > 1 else None
+    for k, x in enumerate(series):
+        x = x if (x.shape[1] == 1 or x.stride(1) == 1) and x.dtype == torch.float64 else x.to(torch.float64).contiguous()
+        ops.chain_mean_var(x, None, mean[k], None if var is None else var[k])
+    return nested_rhat_from_moments(mean, None if var is None else var * float(n - 1), n, M, ops, group)
+
+
+def nested_rhat(chains, chains_per_superchain: int, *, ops=None, group=None):
+    """Nested R-hat of one quantity (see the note above ``nested_rhat_from_moments``).
+
+    ``chains``: a device tensor [N, C], or a sequence of equal-length 1-D chains; chains k M .. k M + M - 1 form
+    superchain k (M = ``chains_per_superchain``).  With a process group ``chains`` is this rank's shard (whole
+    superchains) and the statistic is over all ranks.  Defined from N = 1 on when M >= 2."""
+    ops = _ops(ops)
+    if _is_matrix(chains):
+        x = chains
+    else:
+        arrs = [np.asarray(c, dtype=np.float64).reshape(-1) for c in chains]
+        if len({a.shape[0] for a in arrs}) > 1:
+            raise ValueError("nested_rhat requires chains of equal length")
+        n0 = arrs[0].shape[0] if arrs else 0
+        host = np.stack(arrs, axis=1) if arrs else np.zeros((n0, 0))
+        x = torch.from_numpy(np.ascontiguousarray(host)).to(ops.device)
+    if x.shape[0] < 1:
+        raise ValueError("nested_rhat requires len(chain) >= 1 for every chain in chains")
+    return np.float64(_nested_rhat_of_series([x], int(chains_per_superchain), ops, group)[0])
+
+
+def superchain_init(points, chains_per_superchain: int):
+    """(K, D) start points -> the (K M, D) ``init`` every sampler takes: point k repeated M = ``chains_per_superchain``
+    times, contiguously, so that chain c starts at ``points[c // M]`` -- the c -> c // M convention of ``nested_rhat``.
+    The M subchains of a superchain differ only by their random streams, which the samplers key by chain id."""
+    M = int(chains_per_superchain)
+    if M < 1:
+        raise ValueError(f"superchain_init requires chains_per_superchain >= 1, but chains_per_superchain = {M}")
+    if isinstance(points, torch.Tensor):
+        if points.dim() != 2:
+            raise ValueError(f"superchain_init takes (K, D) start points, got shape {tuple(points.shape)}")
+        return points.repeat_interleave(M, dim=0)
+    p = np.asarray(points, dtype=np.float64)
+    if p.ndim != 2:
+        raise ValueError(f"superchain_init takes (K, D) start points, got shape {p.shape}")
+    return np.repeat(p, M, axis=0)
+
+
 def _as_dc(theta, D: int, C: int, layout=None):
     """A sampler's draw as a logical [D, C] tensor.  ``sample()`` returns the (C, D) transpose view of the
     engine's [D, C] buffer.  For C != D the shape tells the two apart; for a square draw the strides do
@@ -148,6 +265,11 @@ class RunningMoments:
 
     def rhat(self, group=None) -> np.ndarray:
         return rhat_from_moments(self.mean, self.m2, self.n, self._ops, group)
+
+    def nested_rhat(self, chains_per_superchain: int, group=None) -> np.ndarray:
+        """Per-dimension nested R-hat over superchains of ``chains_per_superchain`` consecutive chains (of all ranks):
+        defined from the first draw on (nested_rhat_from_moments)."""
+        return nested_rhat_from_moments(self.mean, self.m2, self.n, chains_per_superchain, self._ops, group)
 
     def pooled_variance(self, group=None) -> np.ndarray:
         """Per-dimension variance of all draws seen so far, pooled over the chains of all ranks:
@@ -346,6 +468,14 @@ class DrawRecorder:
     def rhat(self, group=None) -> np.ndarray:
         """R-hat (rhat.py:111-171) of every tracked quantity over all chains (and ranks)."""
         return np.array([rhat(self.view(k), ops=self._ops, group=group) for k in range(self.series.shape[0])])
+
+    def nested_rhat(self, chains_per_superchain: int, group=None) -> np.ndarray:
+        """Nested R-hat of every tracked quantity over superchains of ``chains_per_superchain`` consecutive chains (of
+        all ranks), from the stored series; works from one recorded draw on."""
+        if self.n < 1:
+            raise ValueError("nested_rhat requires len(chain) >= 1 for every chain in chains")
+        series = [self.view(k) for k in range(self.series.shape[0])]
+        return _nested_rhat_of_series(series, int(chains_per_superchain), self._ops, group)
 
     def summary(self, group=None) -> dict:
         """Per tracked quantity (arrays in ``names()`` order): ``name``, ``mean`` and ``sd`` (ddof = 1) of the split set,

@@ -75,6 +75,150 @@ __global__ __launch_bounds__(256) void k_rhat_partials(const double* mean, const
   }
 }
 
+// ---- nested R-hat: the moments of every superchain (bk_superchain_moments) ---------------------------------------------
+// Superchain k of a row is the M consecutive chains k M .. k M + M - 1.  Per row d and superchain k
+//     s = (sum_m mu_m) / M          Wt = (sum_m M2_m / (n - 1)) / M     (each quotient rounded, then added; 0 for n = 1)
+//     Bt = (sum_m (mu_m - s)^2) / (M - 1)   (0 for M = 1)               s_out = s,  w_out = Bt + Wt
+// centred on the ROUNDED s.  All three sums of one superchain take the same order, which depends on M and on a chain's
+// index m INSIDE its superchain only -- never on k, ld, the row or the launch geometry -- so a superchain's two doubles
+// are the same bits wherever it sits in the array (another K, another pitch, a view that begins at a superchain boundary:
+// one rank or several).  No workgroup reads what another wrote; no floating-point atomics.  Three launch shapes:
+//
+// k_superchain_seg, M = 2^j <= 64: lane = chain, loads coalesced, 64 / M superchains per wavefront (256 % M == 0 and
+//   C % M == 0: no superchain straddles a wavefront or the end of the row).  Order: the xor butterfly of bke::wave_sum
+//   stopped at M, v = v + v[m ^ 1], .. ^ 2, .., ^ M / 2 -- lane m adds its partner m ^ stride at every level, so all M
+//   lanes end with the same bits (sc_segment_sum: DPP moves inside a row of 16 lanes, ds_bpermute across rows).  mu
+//   stays in its register for the centred sum.  SC_ROWS rows per workgroup, their loads issued before the first butterfly.
+// k_superchain_wg, M > 64: one workgroup of 256 per (superchain, row).  Order: k_rhat_partials' -- thread t adds chains
+//   m = t, t + 256, .. in that order, the 256 sums are halved 128, 64, .. 1 in LDS.  The centred pass reads mean AGAIN from
+//   global memory: the 8 M bytes this workgroup loaded a moment ago, served by the L2 (the CU's vector L1 when they still
+//   sit there), not by HBM and not kept in registers or LDS.
+// k_superchain_lane, every other M (3, 5, 6, .. 63): lane = superchain, sequential in m = 0, 1, .. M - 1; the centred pass
+//   re-reads its M doubles through L1 / L2.  Lanes stride by 8 M bytes: the simple path, correct for any M.
+constexpr int SC_ROWS = 4;
+
+// v of the lane a DPP move pairs this one with, inside its row of 16 lanes (no LDS traffic, unlike ds_bpermute)
+template <int CTRL>
+__device__ __forceinline__ double sc_dpp(double v) {
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, false);
+  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, false);
+  return __hiloint2double(hi, lo);
+}
+
+// The xor butterfly over the M = 2^j <= 64 lanes of a segment, v = v + v[lane ^ 1], .. ^ 2, .. ^ M / 2.  Strides 1 and 2 are
+// quad permutes; strides 4 and 8 take the row's half-mirror (lane 7 - i of the eight) and mirror (15 - i of the sixteen)
+// instead of lane ^ 4 and lane ^ 8: after the level of stride h all 2 h lanes of a group hold the same bits, so ANY lane of
+// the partner group carries the xor partner's value and the sum is the same double.  Strides 16 and 32 cross rows:
+// ds_bpermute (__shfl_xor).  With all six levels through ds_bpermute the kernel was bound by the LDS pipe, not by HBM
+// (M = 64 at 1,024 x 65,536: 0.40 ms against 0.27 for M = 2).  Every lane of the wavefront must be active.
+__device__ __forceinline__ double sc_segment_sum(double v, int M) {
+  if (M > 1) v = v + sc_dpp<0xB1>(v);   // quad_perm [1, 0, 3, 2]
+  if (M > 2) v = v + sc_dpp<0x4E>(v);   // quad_perm [2, 3, 0, 1]
+  if (M > 4) v = v + sc_dpp<0x141>(v);  // row_half_mirror
+  if (M > 8) v = v + sc_dpp<0x140>(v);  // row_mirror
+  if (M > 16) v = v + __shfl_xor(v, 16);
+  if (M > 32) v = v + __shfl_xor(v, 32);
+  return v;
+}
+
+__global__ __launch_bounds__(256) void k_superchain_seg(const double* mean, const double* m2, i64 ld, double nm1, int M,
+                                                        int lgM, double* s_out, double* w_out, i64 ldk, i64 C, i64 D) {
+  const i64 c = (i64)blockIdx.x * 256 + threadIdx.x;
+  const bool in = c < C;  // (whole superchains are in or out; every lane stays for the exchanges)
+  const bool head = (threadIdx.x & (M - 1)) == 0;
+  const double fM = (double)M;
+  for (i64 d0 = (i64)blockIdx.y * SC_ROWS; d0 < D; d0 += (i64)gridDim.y * SC_ROWS) {
+    double mu[SC_ROWS], q[SC_ROWS];
+#pragma unroll
+    for (int i = 0; i < SC_ROWS; ++i) {
+      const bool ok = in && d0 + i < D;
+      mu[i] = ok ? mean[(d0 + i) * ld + c] : 0.0;
+      q[i] = (ok && m2) ? m2[(d0 + i) * ld + c] : 0.0;
+    }
+#pragma unroll
+    for (int i = 0; i < SC_ROWS; ++i) {
+      const double s = sc_segment_sum(mu[i], M) / fM;
+      const double v = sc_segment_sum(m2 ? q[i] / nm1 : 0.0, M);
+      const double dv = mu[i] - s;
+      const double b = sc_segment_sum(dv * dv, M);
+      const double bt = M > 1 ? b / (fM - 1.0) : 0.0;
+      if (in && head && d0 + i < D) {
+        s_out[(d0 + i) * ldk + (c >> lgM)] = s;
+        w_out[(d0 + i) * ldk + (c >> lgM)] = bt + v / fM;
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_superchain_wg(const double* mean, const double* m2, i64 ld, double nm1, i64 M,
+                                                       double* s_out, double* w_out, i64 ldk, i64 D) {
+  __shared__ double red[2][256];
+  const i64 k = blockIdx.x;
+  const int t = threadIdx.x;
+  const double fM = (double)M;
+  for (i64 d = blockIdx.y; d < D; d += gridDim.y) {
+    const double* mu = mean + d * ld + k * M;
+    const double* qq = m2 ? m2 + d * ld + k * M : nullptr;
+    double s0 = 0.0, s1 = 0.0;
+    for (i64 j = t; j < M; j += 256) {
+      s0 = s0 + mu[j];
+      if (qq) s1 = s1 + qq[j] / nm1;
+    }
+    red[0][t] = s0;
+    red[1][t] = s1;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+      if (t < w) {
+        red[0][t] += red[0][t + w];
+        red[1][t] += red[1][t + w];
+      }
+      __syncthreads();
+    }
+    const double s = red[0][0] / fM, wt = red[1][0] / fM;
+    __syncthreads();
+    double b = 0.0;
+    for (i64 j = t; j < M; j += 256) {
+      const double dv = mu[j] - s;
+      b = b + dv * dv;
+    }
+    red[0][t] = b;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+      if (t < w) red[0][t] += red[0][t + w];
+      __syncthreads();
+    }
+    if (t == 0) {
+      s_out[d * ldk + k] = s;
+      w_out[d * ldk + k] = red[0][0] / (fM - 1.0) + wt;
+    }
+    __syncthreads();  // (red is written again by the next row)
+  }
+}
+
+__global__ __launch_bounds__(256) void k_superchain_lane(const double* mean, const double* m2, i64 ld, double nm1, i64 M,
+                                                         double* s_out, double* w_out, i64 ldk, i64 K, i64 D) {
+  const i64 k = (i64)blockIdx.x * 256 + threadIdx.x;
+  if (k >= K) return;
+  const double fM = (double)M;
+  for (i64 d = blockIdx.y; d < D; d += gridDim.y) {
+    const double* mu = mean + d * ld + k * M;
+    const double* qq = m2 ? m2 + d * ld + k * M : nullptr;
+    double s = 0.0, v = 0.0;
+    for (i64 j = 0; j < M; ++j) {
+      s = s + mu[j];
+      if (qq) v = v + qq[j] / nm1;
+    }
+    s = s / fM;
+    double b = 0.0;
+    for (i64 j = 0; j < M; ++j) {
+      const double dv = mu[j] - s;
+      b = b + dv * dv;
+    }
+    s_out[d * ldk + k] = s;
+    w_out[d * ldk + k] = (M > 1 ? b / (fM - 1.0) : 0.0) + v / fM;
+  }
+}
+
 // two-pass mean / variance per chain of a stored series (np.mean, np.var(ddof=1)): a workgroup of four wavefronts
 // serves 64 chains (lane = chain); wavefront w sums the draws t = w, w + 4, w + 8, ... with eight loads in flight,
 // the four partial sums are combined as ((p0 + p1) + p2) + p3.  (One lane walking its chain's N rows alone, one load
@@ -657,6 +801,32 @@ int bk_rhat_partials(const double* mean, const double* m2, int64_t ld, int64_t n
   if (D == 0) return BK_OK;
   k_rhat_partials<<<dim3((unsigned)D), dim3(256), 0, bk_stream(stream)>>>(mean, m2, ld, (double)(n - 1), center,
                                                                         out, C, D);
+  BK_RETURN_LAUNCH_STATUS();
+}
+
+int bk_superchain_moments(const double* mean, const double* m2, int64_t ld, int64_t n, int64_t M, double* s_out,
+                          double* w_out, int64_t ldk, int64_t C, int64_t D, void* stream) {
+  if (!mean || !s_out || !w_out || (!m2 && n > 1) || M < 1 || n < 1 || C < 0 || D < 0) return BK_E_ARG;
+  if (C % M != 0) return BK_E_ARG;
+  const i64 K = C / M;
+  if (ld < C || ldk < K) return BK_E_ALIGN;
+  if (C == 0 || D == 0) return BK_OK;
+  if (K > 0x7fffffff) return BK_E_ARG;
+  if (n == 1) m2 = nullptr;  // (Wt = 0: M2 is not read)
+  const double nm1 = (double)(n - 1);
+  hipStream_t s = bk_stream(stream);
+  const i64 rows = D < 65535 ? D : 65535;  // (the kernels stride over the rows a grid's y extent does not reach)
+  if (M <= BK_WAVE && (M & (M - 1)) == 0) {
+    int lg = 0;
+    while (((i64)1 << lg) < M) ++lg;
+    dim3 grid((unsigned)bk_cdiv(C, 256), (unsigned)(bk_cdiv(D, SC_ROWS) < 65535 ? bk_cdiv(D, SC_ROWS) : 65535));
+    k_superchain_seg<<<grid, dim3(256), 0, s>>>(mean, m2, ld, nm1, (int)M, lg, s_out, w_out, ldk, C, D);
+  } else if (M > BK_WAVE) {
+    k_superchain_wg<<<dim3((unsigned)K, (unsigned)rows), dim3(256), 0, s>>>(mean, m2, ld, nm1, M, s_out, w_out, ldk, D);
+  } else {
+    k_superchain_lane<<<dim3((unsigned)bk_cdiv(K, 256), (unsigned)rows), dim3(256), 0, s>>>(mean, m2, ld, nm1, M, s_out,
+                                                                                          w_out, ldk, K, D);
+  }
   BK_RETURN_LAUNCH_STATUS();
 }
 

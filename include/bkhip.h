@@ -864,6 +864,21 @@ int bk_record_series_dev(const double* theta, int64_t ld, const int32_t* dims, i
 int bk_rhat_partials(const double* mean, const double* m2, int64_t ld, int64_t n,
                      const double* center, double* out, int64_t C, int64_t D, void* stream);
 
+/* Per-superchain moments for nested R-hat (Margossian et al., "Nested R-hat: assessing the convergence of Markov chain
+ * Monte Carlo when running many short chains"): superchain k of a row is the M consecutive chains k*M .. k*M + M - 1 of
+ * the [D][ld] Welford moments (n draws per chain), K = C / M superchains per row.
+ *     s_out[d*ldk + k] = s  = (sum_m mean) / M
+ *     w_out[d*ldk + k] = Bt + Wt,  Bt = sum_m (mean - s)^2 / (M - 1)  (0 for M = 1; centred on the rounded s),
+ *                                  Wt = (sum_m m2 / (n - 1)) / M      (0 for n = 1: m2 is not read and may be NULL)
+ * The order of every sum depends on M and on a chain's index inside its superchain only: M = 2^j <= 64 the xor butterfly
+ * with strides 1, 2, .. M/2; M > 64 bk_rhat_partials' order inside the superchain (thread t adds m = t, t+256, .. in order,
+ * the 256 sums are halved 128, 64, .. 1); any other M sequentially in m.  So a superchain's two doubles are the same bits
+ * on every run and wherever it sits (other K, ld, a view that starts at a superchain boundary).  No floating-point
+ * atomics.  NaN, infinities and a zero w_out are what IEEE arithmetic gives; nothing is filtered.
+ * M < 1, n < 1, C % M != 0, a NULL array: BK_E_ARG; ld < C or ldk < K: BK_E_ALIGN; C == 0 or D == 0: BK_OK, no launch. */
+int bk_superchain_moments(const double* mean, const double* m2, int64_t ld, int64_t n, int64_t M, double* s_out,
+                          double* w_out, int64_t ldk, int64_t C, int64_t D, void* stream);
+
 /* The acceptance statistic a step-size adaptation averages, before the accept test overwrites lp_cur:
  *     d_c    = (lp_prop[c] - a_prop[c]) - (lp_cur[c] - a_cur[c])      the h1 - h0 of bk_mh_accept in HMC mode
  *     out[0] = sum_c min(1, bk_exp(min(0, d_c)))   over the chains whose d_c is not NaN
