@@ -19,6 +19,7 @@ from .ess import ess, ess_imse, ess_ipse
 from .iat import iat, iat_imse, iat_ipse
 from .rhat import rank_normalized_rhat, rhat, split_rhat
 from .ensemble import Stretcher
+from .tempering import TemperedStretcher, geometric_ladder
 from .drghmc import DrGhmcDiag
 from .hmc import HMCDiag
 from .mala import MALA
@@ -34,6 +35,8 @@ __all__ = [
     "MetropolisHastings",
     "TemperedLikelihoodSMC",
     "Stretcher",
+    "TemperedStretcher",
+    "geometric_ladder",
     "ess",
     "ess_imse",
     "ess_ipse",

@@ -46,6 +46,8 @@ SIGNATURES = {
     "bk_select_columns": [P, P, P, P, P, P, I, I, I, P],
     "bk_blend_columns": [P, P, P, P, I, I, I, P],
     "bk_stretch_propose": [P, I, I, I, I, I, P, P, F, F, P, I, P, P, I, P],
+    "bk_tempered_accept": [P, P, P, P, P, P, P, P, P, I, I, P],
+    "bk_replica_swap": [P, P, I, P, P, P, P, P, P, P, P, I, I, I, P],
     "bk_leapfrog_kick_drift_ld": [P, I, P, I, P, I, P, I, P, I, I, P, F, c_int, F, c_int, F, I, I, P],
     "bk_blend_columns_ld": [P, P, I, P, I, P, I, I, I, P],
     "bk_select_columns_ld": [P, P, I, P, I, I, I, P],
@@ -468,6 +470,32 @@ class Ops:
         self._call("bk_stretch_propose", ptr(theta), _ld(theta), int(col_act), int(col_oth), int(n), int(H), ptr(u_j),
                    ptr(u_z), float(inv_sqrt_a), float(sqrt_a), ptr(theta_prop), _ld(theta_prop), ptr(zterm), ptr(partner), D,
                    self._s())
+
+    def tempered_accept(self, ll, lp0, ll_prop, lp0_prop, beta, zterm, log_u, mask, counts, H):
+        """log_u < ((lp0_prop - lp0) + beta * (ll_prop - ll)) + zterm on the n columns of these slices (lp0 / lp0_prop may
+        be None: the literal 0.0); accepted columns take the proposal's ll (and lp0); counts: int32 [n / H] or None, the
+        accepted columns of every block of H.  bk_tempered_accept."""
+        n = ll.shape[0]
+        assert min(ll_prop.numel(), beta.numel(), zterm.numel(), log_u.numel(), mask.numel()) >= n
+        assert (lp0 is None) == (lp0_prop is None) and mask.dtype == torch.uint8
+        assert counts is None or (counts.dtype == torch.int32 and counts.numel() * int(H) >= n)
+        self._call("bk_tempered_accept", ptr(ll), ptr(lp0), ptr(ll_prop), ptr(lp0_prop), ptr(beta), ptr(zterm), ptr(log_u),
+                   ptr(mask), ptr(counts), n, int(H), self._s())
+
+    def replica_swap(self, theta, theta2, ll, lp0, beta, log_u, lower, swapped, proposed, accepted, H):
+        """Every column c with lower[c] proposes to change places with column c + H: theta (and theta2, of the same pitch,
+        or None), ll and lp0 (or None) are exchanged where log_u[c] < (beta[c] - beta[c + H]) * (ll[c + H] - ll[c]);
+        swapped [C] uint8; proposed / accepted: int32 [C / H] or None.  bk_replica_swap."""
+        D, C = theta.shape
+        ld = _ld(theta)
+        assert theta2 is None or (tuple(theta2.shape) == (D, C) and _ld(theta2) == ld)
+        assert min(ll.numel(), beta.numel(), log_u.numel(), lower.numel(), swapped.numel()) >= C
+        assert lp0 is None or lp0.numel() >= C
+        assert lower.dtype == torch.uint8 and swapped.dtype == torch.uint8
+        for cnt in (proposed, accepted):
+            assert cnt is None or (cnt.dtype == torch.int32 and cnt.numel() * int(H) >= C)
+        self._call("bk_replica_swap", ptr(theta), ptr(theta2), ld, ptr(ll), ptr(lp0), ptr(beta), ptr(log_u), ptr(lower),
+                   ptr(swapped), ptr(proposed), ptr(accepted), C, int(H), D, self._s())
 
     # -- delayed rejection ---------------------------------------------------------------------
     # n_dev (optional, everywhere below): int32 device tensor [1] holding the number of lanes really

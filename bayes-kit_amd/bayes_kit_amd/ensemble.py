@@ -14,7 +14,8 @@ One ``sample()`` is two half-updates, ``s = 0`` then ``s = 1``.  Each active wal
 stream (``numpy.random.Philox(key=[seed, chain_id0 + column])``), in the order ``u_j`` (partner), ``u_z`` (stretch), ``u_a``
 (accept); inactive walkers draw nothing, so after ``n`` draws every stream stands ``3 n`` uniforms further.  The proposal is
 the ``bk_stretch_propose`` kernel (include/bkhip.h).  The log density of every walker is cached (the reference's
-``TODO(carpenter)``).
+``TODO(carpenter)``).  ``tempering.TemperedStretcher`` runs the same draw on a ladder of tempered targets: it overrides the
+accept step, the end of a draw and the cached density (``_accept``, ``_end_draw``, ``_init_cache``, ``_logp_out``).
 """
 from __future__ import annotations
 
@@ -94,7 +95,25 @@ class Stretcher(ManyChainSampler):
             act[s * n:(s + 1) * n] = 1
             self._active.append(act)
         self._draws = 0
+        self._init_cache()
+
+    # -- the target: what a subclass with another one overrides (TemperedStretcher) ------------------------------------
+    def _init_cache(self):
+        """The cached log density of every walker at the start."""
         self._eval_logp(self._theta_dc, self._lp)
+
+    def _accept(self, act):
+        """The density of the proposals of the active slice `act`, and the accept test: the mask, the cache and the counter."""
+        self._eval_logp(self._theta_p[:, act], self._lp_p[act])
+        # log(u_a) < (lp* - lp) + (zterm - 0.0); on acceptance the kernel moves lp* into lp   (ensemble.py:54-57)
+        self._ops.mh_accept(_lib.ACCEPT_MALA, self._lp[act], None, self._lp_p[act], self._zterm[act], self._logu[act],
+                            self._mask[act], None, self._accepted)
+
+    def _end_draw(self, out):
+        """After both half-updates (`_draws` counts this draw); `out` is the copy of the state that sample() returns."""
+
+    def _logp_out(self):
+        return self._lp
 
     # -- state ------------------------------------------------------------------------------------------------------
     def _state_tensors(self):
@@ -147,12 +166,10 @@ class Stretcher(ManyChainSampler):
             ops.log_uniform(self._rng_kind, self._rng_state, self._logu, self._active[s])
             ops.stretch_propose(th, a0, o0, n, H, self._u_j[act], self._u_z[act], self._inv_sqrt_a, self._sqrt_a,
                                 thp[:, act], self._zterm[act], self._partner[act])
-            self._eval_logp(thp[:, act], self._lp_p[act])
-            # log(u_a) < (lp* - lp) + (zterm - 0.0); on acceptance the kernel moves lp* into lp   (ensemble.py:54-57)
-            ops.mh_accept(_lib.ACCEPT_MALA, self._lp[act], None, self._lp_p[act], self._zterm[act], self._logu[act],
-                          self._mask[act], None, self._accepted)
+            self._accept(act)
             # this half stays as it is now for the rest of the draw: its columns of the returned array in the same pass
             ops.select_columns(self._mask[act], th[:, act], thp[:, act], None, None, out[:, act])
         self._draws += 1
+        self._end_draw(out)
         self._out = out
-        return self._draw_out(th, self._lp)
+        return self._draw_out(th, self._logp_out())

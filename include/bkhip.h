@@ -271,6 +271,43 @@ int bk_stretch_propose(const double* theta, int64_t ld, int64_t col_act, int64_t
                        const double* u_j, const double* u_z, double inv_sqrt_a, double sqrt_a, double* theta_prop,
                        int64_t ldp, double* zterm, int32_t* partner, int64_t D, void* stream);
 
+/* ---- parallel tempering (replica exchange): a tempered accept test and the swap of two rungs' columns -----
+ * A column (walker, chain) c targets lp0(theta) + beta[c] * ll(theta); ll and lp0 are cached per column, lp0 may be
+ * absent (NULL: the whole log density is tempered).  beta is a per-column [n] / [C] array.
+ *
+ * bk_tempered_accept, for the n columns the pointers point at (an active slice):
+ *     accept = log_u[k] < ((lp0_prop[k] - lp0[k]) + beta[k] * (ll_prop[k] - ll[k])) + zterm[k]
+ * in exactly that order, every operation rounded on its own; lp0 == NULL: the first term is the literal 0.0 (with
+ * beta = 1 the test is then the one of bk_mh_accept(BK_ACCEPT_MALA, ll, NULL, ll_prop, zterm, ...)).  Strict `<`; a NaN
+ * on either side refuses.  On accept ll[k] <- ll_prop[k] (and lp0[k] <- lp0_prop[k]); accept_mask[k] = 0/1.
+ * accept_counts (device u32 [n / H], may be NULL): entry k / H is incremented by the accepted columns of the k / H-th
+ * block of H columns (an ensemble's active half).  Integer atomics only, so the counts are exact: one per wavefront
+ * where all columns of the wavefront lie in one block (ballot + popcount), one per accepting lane otherwise.
+ * BK_E_ARG: ll, ll_prop, beta, zterm, log_u or accept_mask null, lp0 without lp0_prop, n < 0, H < 1, n % H != 0;
+ * decided before any HIP call.  n == 0: BK_OK, nothing launched.
+ *
+ * bk_replica_swap, on plain [D][ld] arrays and [C] vectors: every column c with lower[c] != 0 and c + H < C proposes to
+ * change places with its partner, column c + H (the caller's pairs are disjoint: no partner is itself a lower column):
+ *     swap = log_u[c] < (beta[c] - beta[c + H]) * (ll[c + H] - ll[c])
+ * IEEE decides the edge cases (0 * inf and -inf - -inf are NaN, and NaN refuses).  If it holds, columns c and c + H of
+ * theta (all D rows, in place), of theta2 (a second array of the same pitch, may be NULL: a cached gradient, the copy
+ * of the state a sampler hands out), of ll and of lp0 (may be NULL) are exchanged.  swapped[c] = 1 for a lower column
+ * that swapped, 0 for every other c < C.  proposed / accepted (device u32 [C / H], each may be NULL): entry c / H is
+ * incremented by the lower columns of that block that proposed / swapped (integer atomics, as above).
+ * The decision reads ll, which the swap overwrites: it is taken once per pair by a [C]-sized pass that writes
+ * `swapped` and exchanges the scalars; the exchange of the columns is a second launch, tiled over blocks of 4 rows, that
+ * reads only `swapped`: one lane per pair, both columns coalesced, loads before stores; two pairs per lane on 16-byte
+ * words where H and ld are even and the array 16-byte aligned; same results.  A refused pair moves no bytes; HBM traffic
+ * 32*D bytes per swapped pair and array.
+ * BK_E_ARG: theta, ll, beta, log_u, lower or swapped null, C < 0, D < 0, H < 1, C % H != 0, ld < C, D > 262,140;
+ * decided before any HIP call.  C == 0: BK_OK, nothing launched. */
+int bk_tempered_accept(double* ll, double* lp0, const double* ll_prop, const double* lp0_prop, const double* beta,
+                       const double* zterm, const double* log_u, uint8_t* accept_mask, uint32_t* accept_counts,
+                       int64_t n, int64_t H, void* stream);
+int bk_replica_swap(double* theta, double* theta2, int64_t ld, double* ll, double* lp0, const double* beta,
+                    const double* log_u, const uint8_t* lower, uint8_t* swapped, uint32_t* proposed, uint32_t* accepted,
+                    int64_t C, int64_t H, int64_t D, void* stream);
+
 /* ---- the same three operations with ONE ROW PITCH PER ARRAY (the tile-major HMC schedule) ---------------
  * A tile of T chains keeps its proposal, momentum and trajectory gradient in contiguous [D][T] arrays that stay
  * in the Infinity Cache, while the state, the generator's momentum and the cached gradient are columns of [D][C]
