@@ -20,6 +20,7 @@ from .iat import iat, iat_imse, iat_ipse
 from .rhat import rank_normalized_rhat, rhat, split_rhat
 from .ensemble import Stretcher
 from .tempering import TemperedStretcher, geometric_ladder
+from .tempered_hmc import TemperedHMC
 from .drghmc import DrGhmcDiag
 from .hmc import HMCDiag
 from .mala import MALA
@@ -36,6 +37,7 @@ __all__ = [
     "TemperedLikelihoodSMC",
     "Stretcher",
     "TemperedStretcher",
+    "TemperedHMC",
     "geometric_ladder",
     "ess",
     "ess_imse",

@@ -48,6 +48,10 @@ SIGNATURES = {
     "bk_stretch_propose": [P, I, I, I, I, I, P, P, F, F, P, I, P, P, I, P],
     "bk_tempered_accept": [P, P, P, P, P, P, P, P, P, I, I, P],
     "bk_replica_swap": [P, P, I, P, P, P, P, P, P, P, P, I, I, I, P],
+    "bk_tempered_kick_drift": [P, P, P, P, I, P, P, I, P, P, P, P, P, I, I, P],
+    "bk_tempered_finish": [P, P, I, P, P, I, P, P, P, P, I, I, P],
+    "bk_tempered_hmc_accept": [P, P, P, P, P, P, P, P, P, P, I, I, P],
+    "bk_exchange_columns": [P, I, P, I, I, I, P],
     "bk_leapfrog_kick_drift_ld": [P, I, P, I, P, I, P, I, P, I, I, P, F, c_int, F, c_int, F, I, I, P],
     "bk_blend_columns_ld": [P, P, I, P, I, P, I, I, I, P],
     "bk_select_columns_ld": [P, P, I, P, I, I, I, P],
@@ -496,6 +500,55 @@ class Ops:
             assert cnt is None or (cnt.dtype == torch.int32 and cnt.numel() * int(H) >= C)
         self._call("bk_replica_swap", ptr(theta), ptr(theta2), ld, ptr(ll), ptr(lp0), ptr(beta), ptr(log_u), ptr(lower),
                    ptr(swapped), ptr(proposed), ptr(accepted), C, int(H), D, self._s())
+
+    @staticmethod
+    def _ldg(grad, grad0, D, C):
+        """The common pitch of the chain-contiguous [D, C] gradients of the tempered integrator."""
+        assert tuple(grad.shape) == (D, C)
+        ldg = _ld(grad)
+        assert grad0 is None or (tuple(grad0.shape) == (D, C) and _ld(grad0) == ldg)
+        return ldg
+
+    def tempered_kick_drift(self, theta_in, theta_out, rho_in, rho_out, grad_ll, grad_lp0, metric, beta, eps, pre, kick):
+        """kick_drift with the force grad_lp0 + beta * grad_ll (grad_lp0 may be None) and per-column [C] vectors beta, eps,
+        pre, kick (pre / kick may be None: no such term); gradients [D, C], chain-contiguous.  bk_tempered_kick_drift."""
+        D, C = theta_out.shape
+        ld = _ld(theta_out)
+        assert _ld(theta_in) == ld and _ld(rho_in) == ld and _ld(rho_out) == ld
+        for v in (beta, eps, pre, kick):
+            assert v is None or (v.is_contiguous() and v.numel() >= C)
+        self._call("bk_tempered_kick_drift", ptr(theta_in), ptr(theta_out), ptr(rho_in), ptr(rho_out), ld, ptr(grad_ll),
+                   ptr(grad_lp0), self._ldg(grad_ll, grad_lp0, D, C), ptr(metric), ptr(beta), ptr(eps), ptr(pre), ptr(kick),
+                   C, D, self._s())
+
+    def tempered_finish(self, rho_in, rho_out, grad_ll, grad_lp0, metric, beta, half, kin_out):
+        """The final half kick rho_in + half * (metric * (grad_lp0 + beta * grad_ll)) (grad_ll None: no kick) into rho_out
+        (or None) and its kinetic energy into kin_out, in leapfrog_finish's summation order.  bk_tempered_finish."""
+        D, C = rho_in.shape
+        assert rho_out is None or _ld(rho_out) == _ld(rho_in)
+        ldg = 0 if grad_ll is None else self._ldg(grad_ll, grad_lp0, D, C)
+        for v in (beta, half):
+            assert v is None or (v.is_contiguous() and v.numel() >= C)
+        self._call("bk_tempered_finish", ptr(rho_in), ptr(rho_out), _ld(rho_in), ptr(grad_ll),
+                   None if grad_ll is None else ptr(grad_lp0), ldg, ptr(metric), ptr(beta), ptr(half), ptr(kin_out), C, D,
+                   self._s())
+
+    def tempered_hmc_accept(self, ll, lp0, kin0, ll_prop, lp0_prop, kin1, beta, log_u, mask, counts, H):
+        """log_u < h1 - h0 with h = (lp0 + beta * ll) - kin at both ends (lp0 / lp0_prop may be None); accepted columns take
+        the proposal's ll (and lp0); counts: int32 [n / H] or None.  bk_tempered_hmc_accept."""
+        n = ll.shape[0]
+        assert min(kin0.numel(), ll_prop.numel(), kin1.numel(), beta.numel(), log_u.numel(), mask.numel()) >= n
+        assert (lp0 is None) == (lp0_prop is None) and mask.dtype == torch.uint8
+        assert counts is None or (counts.dtype == torch.int32 and counts.numel() * int(H) >= n)
+        self._call("bk_tempered_hmc_accept", ptr(ll), ptr(lp0), ptr(kin0), ptr(ll_prop), ptr(lp0_prop), ptr(kin1), ptr(beta),
+                   ptr(log_u), ptr(mask), ptr(counts), n, int(H), self._s())
+
+    def exchange_columns(self, x, swapped, H):
+        """Columns c and c + H of the [D, C] array x change places where swapped[c]: a swap round that replica_swap decided,
+        applied to one further array.  bk_exchange_columns."""
+        D, C = x.shape
+        assert swapped.dtype == torch.uint8 and swapped.numel() >= C
+        self._call("bk_exchange_columns", ptr(x), _ld(x), ptr(swapped), C, int(H), D, self._s())
 
     # -- delayed rejection ---------------------------------------------------------------------
     # n_dev (optional, everywhere below): int32 device tensor [1] holding the number of lanes really

@@ -594,3 +594,19 @@ class TorchPriorLikelihoodModel:
 
     def log_density_gradient(self, Theta):
         return self.log_density_gradient_tempered(Theta, 1.0)
+
+    @staticmethod
+    def _value_and_gradient(f, Theta):
+        x = Theta.detach().requires_grad_(True)
+        with torch.enable_grad():
+            v = f(x)
+            (g,) = torch.autograd.grad(v.sum(), x)
+        return v.detach(), g
+
+    def log_prior_gradient(self, Theta):
+        """-> (log prior (M,), its gradient (M, D)): one of the two parts ``TemperedHMC`` tempers separately."""
+        return self._value_and_gradient(self._lp, Theta)
+
+    def log_likelihood_gradient(self, Theta):
+        """-> (log likelihood (M,), its gradient (M, D))."""
+        return self._value_and_gradient(self._ll, Theta)

@@ -308,6 +308,63 @@ int bk_replica_swap(double* theta, double* theta2, int64_t ld, double* ll, doubl
                     const double* log_u, const uint8_t* lower, uint8_t* swapped, uint32_t* proposed, uint32_t* accepted,
                     int64_t C, int64_t H, int64_t D, void* stream);
 
+/* ---- the leapfrog integrator of a ladder (tempered HMC): per-column inverse temperature and step size -------
+ * Column c targets lp0(theta) + beta[c] * ll(theta) and integrates with its own step size: beta, eps, pre, kick and half
+ * are per-column [C] device vectors where bk_leapfrog_kick_drift / bk_leapfrog_finish take scalars.  Phase-space arrays
+ * are [D][ld]; the gradients grad_ll and grad_lp0 are chain-contiguous [D][ldg] arrays with a pitch of their own (a
+ * (C, D) row-major model output goes through bk_relayout first).  grad_lp0 may be NULL: the whole log density is
+ * tempered.  metric may be NULL: ones, not multiplied in.  Every `*` and `+` below is rounded on its own.  The force on
+ * element (d, c) is
+ *     f = beta[c] * grad_ll[d*ldg + c] ;   if grad_lp0: f = grad_lp0[d*ldg + c] + f
+ *     t = metric ? metric[d] * f : f
+ *
+ * bk_tempered_kick_drift:
+ *     r = rho_in[d*ld + c] ;   if pre: r = r + pre[c] * t ;   if kick: r = r + kick[c] * t
+ *     rho_out[d*ld + c] = r ;  theta_out[d*ld + c] = theta_in[d*ld + c] + eps[c] * r
+ * pre and kick may be NULL (no such term).  In-place use (theta_out == theta_in, rho_out == rho_in) is allowed: every
+ * element is loaded before it is stored, by one lane.  With beta all 1.0, grad_lp0 NULL and uniform vectors the result
+ * is bk_leapfrog_kick_drift's bit for bit (1.0 * g is g).  HBM traffic 40 bytes per element, 48 with grad_lp0; the
+ * per-column vectors are 8*C bytes each, read once per workgroup and 4 rows and served from cache.
+ *
+ * bk_tempered_finish:
+ *     r = grad_ll ? rho_in[d*ld + c] + half[c] * t : rho_in[d*ld + c] ;   if rho_out: rho_out[d*ld + c] = r
+ *     kin_out[c] = 0.5 * sum_d r * (metric ? metric[d] * r : r)
+ * summed in bk_leapfrog_finish's order: four contiguous quarters of d (ceil(D / 4) rows each), sequentially inside each,
+ * combined as ((p0 + p1) + p2) + p3.  rho_out and kin_out may be NULL; beta and half are not read without grad_ll.  In the
+ * degenerate case above the result is bk_leapfrog_finish(negate = 0)'s bit for bit.  HBM traffic 16 bytes per element, 24
+ * with grad_lp0, 8 more with rho_out.
+ *
+ * Both choose between two forms by shape: C, ld, ldg even and every array and vector 16-byte aligned -> two columns
+ * (16 bytes) per lane, each with its own entry of the vectors; anything else one column per lane; same results.
+ *
+ * bk_tempered_hmc_accept, for n columns:
+ *     h0 = (lp0 ? lp0[k] + beta[k] * ll[k] : beta[k] * ll[k]) - kin0[k]
+ *     h1 = (lp0 ? lp0_prop[k] + beta[k] * ll_prop[k] : beta[k] * ll_prop[k]) - kin1[k]
+ *     accept = log_u[k] < h1 - h0
+ * Strict `<`; a NaN on either side refuses (0 * inf is NaN).  At beta = 1 without lp0 this is the comparison of
+ * bk_mh_accept(BK_ACCEPT_HMC) exactly.  On accept ll[k] <- ll_prop[k] (and lp0[k] <- lp0_prop[k]); accept_mask[k] = 0/1;
+ * accept_counts (device u32 [n / H], may be NULL) as in bk_tempered_accept: exact integer atomics per block of H columns.
+ *
+ * bk_exchange_columns: columns c and c + H of x change places where swapped[c] != 0, for c < C - H: the exchange pass
+ * of bk_replica_swap on one further array, after the decision (which overwrote ll and cannot be repeated) was taken.
+ * Same two forms and traffic (32*D bytes per swapped pair) as there.
+ *
+ * Errors, decided before any HIP call.  BK_E_ARG: a null required pointer (kick_drift: theta_in, theta_out, rho_in,
+ * rho_out, grad_ll, beta, eps; finish: rho_in, and beta and half with grad_ll; accept: ll, kin0, ll_prop, kin1, beta,
+ * log_u, accept_mask, lp0 without lp0_prop; exchange: x, swapped), a negative extent, H < 1, n % H != 0 or C % H != 0,
+ * D > 262,140 (kick_drift, exchange).  BK_E_ALIGN: ld < C or ldg < C.  C == 0, D == 0 or n == 0: BK_OK, nothing launched. */
+int bk_tempered_kick_drift(const double* theta_in, double* theta_out, const double* rho_in, double* rho_out, int64_t ld,
+                           const double* grad_ll, const double* grad_lp0, int64_t ldg, const double* metric,
+                           const double* beta, const double* eps, const double* pre, const double* kick, int64_t C,
+                           int64_t D, void* stream);
+int bk_tempered_finish(const double* rho_in, double* rho_out, int64_t ld, const double* grad_ll, const double* grad_lp0,
+                       int64_t ldg, const double* metric, const double* beta, const double* half, double* kin_out,
+                       int64_t C, int64_t D, void* stream);
+int bk_tempered_hmc_accept(double* ll, double* lp0, const double* kin0, const double* ll_prop, const double* lp0_prop,
+                           const double* kin1, const double* beta, const double* log_u, uint8_t* accept_mask,
+                           uint32_t* accept_counts, int64_t n, int64_t H, void* stream);
+int bk_exchange_columns(double* x, int64_t ld, const uint8_t* swapped, int64_t C, int64_t H, int64_t D, void* stream);
+
 /* ---- the same three operations with ONE ROW PITCH PER ARRAY (the tile-major HMC schedule) ---------------
  * A tile of T chains keeps its proposal, momentum and trajectory gradient in contiguous [D][T] arrays that stay
  * in the Infinity Cache, while the state, the generator's momentum and the cached gradient are columns of [D][C]
