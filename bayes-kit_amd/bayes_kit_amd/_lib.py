@@ -21,6 +21,8 @@ RNG_PHILOX = 0
 RNG_PCG64 = 1
 ACCEPT_HMC = 0
 ACCEPT_MALA = 1
+BK_RESAMPLE_SYSTEMATIC = 0
+BK_RESAMPLE_STRATIFIED = 1
 
 P = c_void_p
 I = c_int64
@@ -105,6 +107,8 @@ SIGNATURES = {
     "bk_logistic_finish": [P, P, I, P, I, F, F, P, P, P, I, I, P],
     "bk_dot_columns": [P, P, I, F, P, I, I, P],
     "bk_resample_indices": [P, I, P, I, P, P, P],
+    "bk_resample_ordered_work_bytes": [I],
+    "bk_resample_ordered": [P, I, P, I, I, I, c_int, P, I, P, P],
     "bk_gather_columns": [P, P, I, P, I, I, I, P],
     "bk_relayout": [P, I, I, P, I, I, I, I, P],
     "bk_welford_update": [P, P, I, P, I, I, I, I, P],
@@ -142,7 +146,7 @@ SIGNATURES = {
     "bk_host_log1p": [F],
     "bk_host_exp": [F],
 }
-_RESTYPE = {"bk_gemm_chains_work_elems": c_int64, "bk_cov_k_chunk": c_int64, "bk_cov_accumulate_work_elems": c_int64, "bk_host_log1p": c_double, "bk_host_exp": c_double, "bk_refresh_work_elems": c_int64, "bk_sort_by_key_work_bytes": c_int64,
+_RESTYPE = {"bk_gemm_chains_work_elems": c_int64, "bk_cov_k_chunk": c_int64, "bk_cov_accumulate_work_elems": c_int64, "bk_host_log1p": c_double, "bk_host_exp": c_double, "bk_refresh_work_elems": c_int64, "bk_sort_by_key_work_bytes": c_int64, "bk_resample_ordered_work_bytes": c_int64,
              "bk_autocorr_fft_work_bytes": c_int64, "bk_ess_multi_work_bytes": c_int64, "bk_ess_lag_sums_max_half": c_int64}
 
 
@@ -976,6 +980,19 @@ class Ops:
     def resample_indices(self, weights, u, cdf_work, idx_out):
         self._call("bk_resample_indices", ptr(weights), weights.shape[0], ptr(u), u.shape[0], ptr(cdf_work),
                    ptr(idx_out), self._s())
+
+    def resample_ordered_work_bytes(self, n):
+        nb = self.lib.bk_resample_ordered_work_bytes(int(n))
+        if nb < 0:
+            raise BkHipError("bk_resample_ordered_work_bytes failed")
+        return int(nb)
+
+    def resample_ordered(self, weights, u, mode, slot0, m_total, work, idx_out):
+        """Systematic (u: one uniform) or stratified (u: one per slot of idx_out) ancestors of the global slots slot0 ..
+        slot0 + len(idx_out) - 1 of m_total, from the fixed-point cumulative weights; work: a uint8 tensor of
+        resample_ordered_work_bytes(len(weights)) bytes, which holds Q as int64 from byte 16 on afterwards."""
+        self._call("bk_resample_ordered", ptr(weights), weights.shape[0], ptr(u), idx_out.shape[0], int(slot0), int(m_total),
+                   int(mode), ptr(work), work.numel() * work.element_size(), ptr(idx_out), self._s())
 
     def gather_columns(self, index, src, dst):
         D, m = dst.shape

@@ -917,6 +917,30 @@ int bk_dot_columns(const double* x, const double* y, int64_t ld, double scale, d
 int bk_resample_indices(const double* weights, int64_t n, const double* u, int64_t m,
                         double* cdf_work, int32_t* idx_out, void* stream);
 
+/* Systematic and stratified resampling (EXTENSION, not in the reference) on a fixed-point cumulative weight that is exact
+ * under any summation order, so that the scan is parallel (csrc/bk_resample.hip: a reduce-then-scan of five launches, no
+ * workgroup waiting for another of its launch).  weights[n]: unnormalised, finite, >= 0, at least one > 0 (a weight that is
+ * not > 0 counts as zero).  m_total slots over all ranks, this call draws the m_local slots J = slot0 + j:
+ *     wmax = max_i w_i,  s = 62 - bit_length(n - 1),  q_i = llrint(ldexp(w_i / wmax, s))   (round to nearest even)
+ *     Q_i = q_0 + .. + q_i  (int64; non-decreasing; the same bits under every tiling),  Q = Q_{n-1} >= 2^s > m_total
+ *     a = Q / m_total, r = Q % m_total,  base_J = J*a + (J*r) / m_total  (= floor(J*Q / m_total)),
+ *     o_J = min(a - 1, (int64) floor(u * (double) a)),   idx_out[j] = #{ i : Q_i <= base_J + o_J }   in [0, n - 1]
+ * BK_RESAMPLE_STRATIFIED: u = u[j], m_local uniforms in [0, 1); BK_RESAMPLE_SYSTEMATIC: u = u[0] for every slot.
+ * No floating-point comparison decides an index: the indices are non-decreasing in J, a particle with q_i = 0 is never
+ * chosen, every stratum [floor(J*Q/m), floor((J+1)*Q/m)) holds exactly one point, and under systematic resampling particle
+ * i gets floor(m q_i / Q) or ceil(m q_i / Q) offspring.  The price of the quantisation: a weight below 2^-(s+1) of the
+ * largest gets no offspring (n = 65,536: s = 46, 7e-15; n = 2^20: s = 42, 1e-13; its expected count was below m times that).
+ * work: caller scratch of bk_resample_ordered_work_bytes(n) bytes (-1 for n > 2^31 - 1, 0 for n <= 0), 16-byte aligned;
+ * afterwards bytes [16, 16 + 8 n) hold Q as int64.
+ * BK_E_ARG: a null pointer, n < 1, m_total < 1, m_local < 0, slot0 < 0, slot0 + m_local > m_total, n or m_total above
+ * 2^31 - 1, an unknown mode, work too small or not 16-byte aligned; decided before any HIP call.  m_local == 0: BK_OK,
+ * nothing launched. */
+#define BK_RESAMPLE_SYSTEMATIC 0
+#define BK_RESAMPLE_STRATIFIED 1
+int64_t bk_resample_ordered_work_bytes(int64_t n);
+int bk_resample_ordered(const double* weights, int64_t n, const double* u, int64_t m_local, int64_t slot0,
+                        int64_t m_total, int mode, void* work, int64_t work_bytes, int32_t* idx_out, void* stream);
+
 /* dst[d*ld_dst + j] = src[d*ld_src + index[j]]: the resampled particles (thetas[idxs]). */
 int bk_gather_columns(const int32_t* index, const double* src, int64_t ld_src, double* dst,
                       int64_t ld_dst, int64_t m, int64_t D, void* stream);
