@@ -20,6 +20,7 @@ from .iat import iat, iat_imse, iat_ipse
 from .rhat import rank_normalized_rhat, rhat, split_rhat
 from .ensemble import Stretcher
 from .tempering import TemperedStretcher, geometric_ladder
+from .differential_evolution import DifferentialEvolution, TemperedDifferentialEvolution
 from .tempered_hmc import TemperedHMC
 from .drghmc import DrGhmcDiag
 from .hmc import HMCDiag
@@ -37,6 +38,8 @@ __all__ = [
     "TemperedLikelihoodSMC",
     "Stretcher",
     "TemperedStretcher",
+    "DifferentialEvolution",
+    "TemperedDifferentialEvolution",
     "TemperedHMC",
     "geometric_ladder",
     "ess",

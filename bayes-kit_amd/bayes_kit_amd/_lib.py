@@ -48,6 +48,7 @@ SIGNATURES = {
     "bk_select_columns": [P, P, P, P, P, P, I, I, I, P],
     "bk_blend_columns": [P, P, P, P, I, I, I, P],
     "bk_stretch_propose": [P, I, I, I, I, I, P, P, F, F, P, I, P, P, I, P],
+    "bk_de_propose": [P, I, I, I, I, I, P, P, P, F, F, P, I, P, P, P, I, P],
     "bk_tempered_accept": [P, P, P, P, P, P, P, P, P, I, I, P],
     "bk_replica_swap": [P, P, I, P, P, P, P, P, P, P, P, I, I, I, P],
     "bk_tempered_kick_drift": [P, P, P, P, I, P, P, I, P, P, P, P, P, I, I, P],
@@ -478,6 +479,18 @@ class Ops:
         self._call("bk_stretch_propose", ptr(theta), _ld(theta), int(col_act), int(col_oth), int(n), int(H), ptr(u_j),
                    ptr(u_z), float(inv_sqrt_a), float(sqrt_a), ptr(theta_prop), _ld(theta_prop), ptr(zterm), ptr(partner), D,
                    self._s())
+
+    def de_propose(self, theta, col_act, col_oth, n, H, u_1, u_2, z, gamma0, sigma, theta_prop, partner1, partner2, gamma):
+        """The differential-evolution move of the n active walkers in columns [col_act, col_act + n) of the state `theta`:
+        each against an ordered pair of different walkers of the other half of its ensemble, columns [col_oth, col_oth + n), H
+        walkers per ensemble half (H >= 2): theta_prop [D, n] (own pitch) = theta_k + gamma (theta_j1 - theta_j2), partner1 and
+        partner2 [n] (int32 columns of theta), gamma [n] = gamma0 (1 + sigma z).  bk_de_propose."""
+        D = theta.shape[0]
+        assert tuple(theta_prop.shape) == (D, n) and partner1.dtype == torch.int32 and partner2.dtype == torch.int32
+        assert min(u_1.numel(), u_2.numel(), z.numel(), partner1.numel(), partner2.numel(), gamma.numel()) >= n
+        self._call("bk_de_propose", ptr(theta), _ld(theta), int(col_act), int(col_oth), int(n), int(H), ptr(u_1), ptr(u_2),
+                   ptr(z), float(gamma0), float(sigma), ptr(theta_prop), _ld(theta_prop), ptr(partner1), ptr(partner2),
+                   ptr(gamma), D, self._s())
 
     def tempered_accept(self, ll, lp0, ll_prop, lp0_prop, beta, zterm, log_u, mask, counts, H):
         """log_u < ((lp0_prop - lp0) + beta * (ll_prop - ll)) + zterm on the n columns of these slices (lp0 / lp0_prop may

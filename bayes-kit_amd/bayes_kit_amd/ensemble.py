@@ -15,7 +15,9 @@ stream (``numpy.random.Philox(key=[seed, chain_id0 + column])``), in the order `
 (accept); inactive walkers draw nothing, so after ``n`` draws every stream stands ``3 n`` uniforms further.  The proposal is
 the ``bk_stretch_propose`` kernel (include/bkhip.h).  The log density of every walker is cached (the reference's
 ``TODO(carpenter)``).  ``tempering.TemperedStretcher`` runs the same draw on a ladder of tempered targets: it overrides the
-accept step, the end of a draw and the cached density (``_accept``, ``_end_draw``, ``_init_cache``, ``_logp_out``).
+accept step, the end of a draw and the cached density (``_accept``, ``_end_draw``, ``_init_cache``, ``_logp_out``);
+``differential_evolution.DifferentialEvolution`` runs another move in the same two half-updates: it overrides the draws and
+the proposal of one half-update (``_propose``).
 """
 from __future__ import annotations
 
@@ -153,19 +155,25 @@ class Stretcher(ManyChainSampler):
         c = torch.arange(self._C, dtype=torch.int64, device=self._ops.device)
         return (c % self._n) // self._H
 
+    # -- the move: what a subclass with another one overrides (differential_evolution) ------------------------------------
+    def _propose(self, s, act):
+        """The draws of the walkers of half `s` from their streams, and their proposals into the slice `act` of `_theta_p`
+        (with `_zterm`, the proposal's term of the accept test, and `_logu`)."""
+        ops, n = self._ops, self._n
+        for u in (self._u_j, self._u_z):
+            ops.uniform(self._rng_kind, self._rng_state, u, self._active[s])
+        ops.log_uniform(self._rng_kind, self._rng_state, self._logu, self._active[s])
+        ops.stretch_propose(self._theta_dc, s * n, (1 - s) * n, n, self._H, self._u_j[act], self._u_z[act],
+                            self._inv_sqrt_a, self._sqrt_a, self._theta_p[:, act], self._zterm[act], self._partner[act])
+
     # -- one draw for every walker --------------------------------------------------------------------------------
     def sample(self):
-        ops, n, H = self._ops, self._n, self._H
+        ops, n = self._ops, self._n
         th, thp = self._theta_dc, self._theta_p
         out = self._new_state()
         for s in (0, 1):
-            a0, o0 = s * n, (1 - s) * n
-            act = slice(a0, a0 + n)
-            for u in (self._u_j, self._u_z):
-                ops.uniform(self._rng_kind, self._rng_state, u, self._active[s])
-            ops.log_uniform(self._rng_kind, self._rng_state, self._logu, self._active[s])
-            ops.stretch_propose(th, a0, o0, n, H, self._u_j[act], self._u_z[act], self._inv_sqrt_a, self._sqrt_a,
-                                thp[:, act], self._zterm[act], self._partner[act])
+            act = slice(s * n, s * n + n)
+            self._propose(s, act)
             self._accept(act)
             # this half stays as it is now for the rest of the draw: its columns of the returned array in the same pass
             ops.select_columns(self._mask[act], th[:, act], thp[:, act], None, None, out[:, act])

@@ -16,6 +16,12 @@
 // XCD's L2 then holds a few row blocks' segments instead of every XCD fetching every segment).  The decode changes which
 // workgroup does which tile, never what is computed: every tile recomputes j and z from the uniforms (a few flops), only
 // row block 0 stores zterm and partner, there are no dependencies between workgroups and no atomics.
+//
+// The differential-evolution move (ter Braak 2006; bk_de_propose) lives here too: the same tiles, decode and launch forms,
+// two gathers per row instead of one.  Active walker k draws an ordered pair (j1, j2), j1 != j2, from the other half of its
+// own ensemble and proposes
+//     theta* = theta_k + g * (theta_j1 - theta_j2),    g = gamma0 * (1.0 + sigma * z)
+// For one row both gathers of a launch fall into the same n * 8 bytes, so the XCD grouping serves them alike.
 #include "bk_common.hpp"
 
 namespace {
@@ -124,6 +130,103 @@ __global__ __launch_bounds__(STRETCH_BLOCK) void k_stretch_v2(const double* __re
     }
 }
 
+struct DeLane {
+  i64 j1, j2;  // the partner pair's columns, never equal
+  double g;    // the step along their difference
+};
+
+__device__ __forceinline__ DeLane de_lane(i64 k, i64 col_oth, i64 H, double u1, double u2, double z, double gamma0,
+                                          double sigma) {
+  // floor(u_1 * H) and floor(u_2 * (H - 1)), each clamped at both ends, then i2 steps over i1: uniform over the ordered
+  // pairs for u in [0, 1), and for ANY input values two different columns of the other half (H >= 2)
+  i64 i1 = (i64)(u1 * (double)H);
+  i1 = i1 > H - 1 ? H - 1 : i1;
+  i1 = i1 < 0 ? 0 : i1;
+  i64 i2 = (i64)(u2 * (double)(H - 1));
+  i2 = i2 > H - 2 ? H - 2 : i2;
+  i2 = i2 < 0 ? 0 : i2;
+  i2 += i2 >= i1 ? 1 : 0;
+  const i64 base = col_oth + (k / H) * H;
+  return {base + i1, base + i2, gamma0 * (1.0 + sigma * z)};
+}
+
+__global__ __launch_bounds__(STRETCH_BLOCK) void k_de(const double* __restrict__ theta, i64 ld, i64 col_act, i64 col_oth,
+                                                      i64 n, i64 H, const double* __restrict__ u_1,
+                                                      const double* __restrict__ u_2, const double* __restrict__ z,
+                                                      double gamma0, double sigma, double* __restrict__ prop, i64 ldp,
+                                                      int32_t* __restrict__ partner1, int32_t* __restrict__ partner2,
+                                                      double* __restrict__ gamma, i64 D, i64 ncb, i64 nrb) {
+  i64 cb, rb;
+  if (!stretch_tile(ncb, nrb, cb, rb)) return;
+  const i64 k = cb * STRETCH_BLOCK + threadIdx.x;
+  if (k >= n) return;
+  const DeLane w = de_lane(k, col_oth, H, u_1[k], u_2[k], z[k], gamma0, sigma);
+  if (rb == 0) {
+    partner1[k] = (int32_t)w.j1;
+    partner2[k] = (int32_t)w.j2;
+    gamma[k] = w.g;
+  }
+  const i64 d0 = rb * STRETCH_ROWS;
+  const double* own = theta + col_act + k;
+  double tk[STRETCH_ROWS], ta[STRETCH_ROWS], tb[STRETCH_ROWS];
+#pragma unroll
+  for (int u = 0; u < STRETCH_ROWS; ++u)
+    if (d0 + u < D) {
+      tk[u] = own[(d0 + u) * ld];
+      ta[u] = theta[(d0 + u) * ld + w.j1];
+      tb[u] = theta[(d0 + u) * ld + w.j2];
+    }
+#pragma unroll
+  for (int u = 0; u < STRETCH_ROWS; ++u)
+    if (d0 + u < D) prop[(d0 + u) * ldp + k] = tk[u] + w.g * (ta[u] - tb[u]);
+}
+
+// two adjacent walkers per lane: n, ld, ldp even, theta + col_act and prop 16-byte aligned
+__global__ __launch_bounds__(STRETCH_BLOCK) void k_de_v2(const double* __restrict__ theta, i64 ld, i64 col_act,
+                                                         i64 col_oth, i64 n2, i64 H, const double* __restrict__ u_1,
+                                                         const double* __restrict__ u_2, const double* __restrict__ z,
+                                                         double gamma0, double sigma, double* __restrict__ prop, i64 ldp,
+                                                         int32_t* __restrict__ partner1, int32_t* __restrict__ partner2,
+                                                         double* __restrict__ gamma, i64 D, i64 ncb, i64 nrb) {
+  i64 cb, rb;
+  if (!stretch_tile(ncb, nrb, cb, rb)) return;
+  const i64 p = cb * STRETCH_BLOCK + threadIdx.x;
+  if (p >= n2) return;
+  const i64 k = 2 * p;
+  const DeLane w0 = de_lane(k, col_oth, H, u_1[k], u_2[k], z[k], gamma0, sigma);
+  const DeLane w1 = de_lane(k + 1, col_oth, H, u_1[k + 1], u_2[k + 1], z[k + 1], gamma0, sigma);
+  if (rb == 0) {
+    partner1[k] = (int32_t)w0.j1;
+    partner1[k + 1] = (int32_t)w1.j1;
+    partner2[k] = (int32_t)w0.j2;
+    partner2[k + 1] = (int32_t)w1.j2;
+    gamma[k] = w0.g;
+    gamma[k + 1] = w1.g;
+  }
+  const i64 d0 = rb * STRETCH_ROWS;
+  const double* own = theta + col_act + k;
+  double2 tk[STRETCH_ROWS];
+  double ta0[STRETCH_ROWS], tb0[STRETCH_ROWS], ta1[STRETCH_ROWS], tb1[STRETCH_ROWS];
+#pragma unroll
+  for (int u = 0; u < STRETCH_ROWS; ++u)
+    if (d0 + u < D) {
+      const double* row = theta + (d0 + u) * ld;
+      tk[u] = *reinterpret_cast<const double2*>(own + (d0 + u) * ld);
+      ta0[u] = row[w0.j1];
+      tb0[u] = row[w0.j2];
+      ta1[u] = row[w1.j1];
+      tb1[u] = row[w1.j2];
+    }
+#pragma unroll
+  for (int u = 0; u < STRETCH_ROWS; ++u)
+    if (d0 + u < D) {
+      double2 o;
+      o.x = tk[u].x + w0.g * (ta0[u] - tb0[u]);
+      o.y = tk[u].y + w1.g * (ta1[u] - tb1[u]);
+      *reinterpret_cast<double2*>(prop + (d0 + u) * ldp + k) = o;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -150,6 +253,30 @@ int bk_stretch_propose(const double* theta, int64_t ld, int64_t col_act, int64_t
   else
     k_stretch<<<grid, dim3(STRETCH_BLOCK), 0, s>>>(theta, ld, col_act, col_oth, n, H, u_j, u_z, inv_sqrt_a, sqrt_a,
                                                    theta_prop, ldp, zterm, partner, D, ncb, nrb);
+  BK_RETURN_LAUNCH_STATUS();
+}
+
+int bk_de_propose(const double* theta, int64_t ld, int64_t col_act, int64_t col_oth, int64_t n, int64_t H,
+                  const double* u_1, const double* u_2, const double* z, double gamma0, double sigma, double* theta_prop,
+                  int64_t ldp, int32_t* partner1, int32_t* partner2, double* gamma, int64_t D, void* stream) {
+  if (!theta || !u_1 || !u_2 || !z || !theta_prop || !partner1 || !partner2 || !gamma) return BK_E_ARG;
+  if (n < 0 || D < 0 || col_act < 0 || col_oth < 0 || H < 2 || n % H != 0) return BK_E_ARG;
+  const i64 columns = (col_act > col_oth ? col_act : col_oth) + n;
+  if (ld < columns || ldp < n || columns > (i64)INT32_MAX) return BK_E_ARG;
+  if (n == 0 || D == 0) return BK_OK;
+  const bool vec = n % 2 == 0 && ld % 2 == 0 && ldp % 2 == 0 && bk_aligned16(theta + col_act) && bk_aligned16(theta_prop);
+  const i64 ncb = bk_cdiv(vec ? n / 2 : n, STRETCH_BLOCK);
+  const i64 nrb = bk_cdiv(D, STRETCH_ROWS);
+  const i64 rows_y = nrb < STRETCH_XCDS ? nrb : bk_cdiv(nrb, STRETCH_XCDS) * STRETCH_XCDS;  // (as bk_stretch_propose)
+  if (ncb > (i64)INT32_MAX || rows_y > 65535) return BK_E_ARG;
+  dim3 grid((unsigned)ncb, (unsigned)rows_y);
+  hipStream_t s = bk_stream(stream);
+  if (vec)
+    k_de_v2<<<grid, dim3(STRETCH_BLOCK), 0, s>>>(theta, ld, col_act, col_oth, n / 2, H, u_1, u_2, z, gamma0, sigma,
+                                                 theta_prop, ldp, partner1, partner2, gamma, D, ncb, nrb);
+  else
+    k_de<<<grid, dim3(STRETCH_BLOCK), 0, s>>>(theta, ld, col_act, col_oth, n, H, u_1, u_2, z, gamma0, sigma, theta_prop,
+                                              ldp, partner1, partner2, gamma, D, ncb, nrb);
   BK_RETURN_LAUNCH_STATUS();
 }
 

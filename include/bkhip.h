@@ -271,6 +271,28 @@ int bk_stretch_propose(const double* theta, int64_t ld, int64_t col_act, int64_t
                        const double* u_j, const double* u_z, double inv_sqrt_a, double sqrt_a, double* theta_prop,
                        int64_t ldp, double* zterm, int32_t* partner, int64_t D, void* stream);
 
+/* ---- differential-evolution move of the ensemble sampler (ter Braak 2006, DE-MC; emcee's DEMove) -----
+ * The layout and the arguments theta, ld, col_act, col_oth, n, H, theta_prop, ldp, D are those of bk_stretch_propose.
+ * Active walker k (ensemble e = k / H) draws an ordered pair of DIFFERENT walkers of the other half of its ensemble from
+ * the uniforms u_1[k], u_2[k], and a step from the standard normal z[k]:
+ *     i1 = clamp((int64)(u_1[k] * H), 0, H - 1)
+ *     i2 = clamp((int64)(u_2[k] * (H - 1)), 0, H - 2);  i2 += (i2 >= i1)     uniform over the H (H - 1) ordered pairs
+ *     j1 = col_oth + e*H + i1 ;  j2 = col_oth + e*H + i2
+ *     g  = gamma0 * (1.0 + sigma * z[k])
+ *     theta_prop[d*ldp + k] = theta[d*ld + col_act + k] + g * (theta[d*ld + j1] - theta[d*ld + j2])
+ *     partner1[k] = j1 ;  partner2[k] = j2 ;  gamma[k] = g
+ * Every operation is rounded on its own.  Both indices are clamped, so ANY values of u_1 and u_2 (NaN, negative, >= 1) give
+ * two different columns of the other half.  The proposal is symmetric: follow with the model's log density at theta_prop
+ * and bk_mh_accept(BK_ACCEPT_MALA, lp, NULL, lp_prop, zeros, log_u, ...) or bk_tempered_accept with a zterm of zeros.
+ * theta is only read; theta_prop must not overlap it.  The two launch forms are chosen as in bk_stretch_propose, with the
+ * same results.  HBM traffic 32*D bytes per active walker when both gathers are served from cache (24*D for the stretch
+ * move): for one d all gathers fall into n*8 contiguous bytes.  Plain loads and stores only.
+ * BK_E_ARG: a null pointer, n < 0, D < 0, a negative column, H < 2, n % H != 0, ld < max(col_act, col_oth) + n, ldp < n,
+ * more than INT32_MAX columns, D > 262,140; decided before any HIP call.  n == 0 or D == 0: BK_OK, nothing launched. */
+int bk_de_propose(const double* theta, int64_t ld, int64_t col_act, int64_t col_oth, int64_t n, int64_t H,
+                  const double* u_1, const double* u_2, const double* z, double gamma0, double sigma, double* theta_prop,
+                  int64_t ldp, int32_t* partner1, int32_t* partner2, double* gamma, int64_t D, void* stream);
+
 /* ---- parallel tempering (replica exchange): a tempered accept test and the swap of two rungs' columns -----
  * A column (walker, chain) c targets lp0(theta) + beta[c] * ll(theta); ll and lp0 are cached per column, lp0 may be
  * absent (NULL: the whole log density is tempered).  beta is a per-column [n] / [C] array.
