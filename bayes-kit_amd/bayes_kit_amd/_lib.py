@@ -118,6 +118,9 @@ SIGNATURES = {
     "bk_welford_update_dev": [P, P, I, P, I, P, I, I, I, P],
     "bk_rhat_partials": [P, P, I, I, P, P, I, I, P],
     "bk_superchain_moments": [P, P, I, I, I, P, P, I, I, I, P],
+    "bk_hist_lds_bins": [],
+    "bk_hist_slab_chains": [I, I, I],
+    "bk_hist_accumulate": [P, I, I, I, P, P, I, P, I, P],
     "bk_accept_stat": [P, P, P, P, I, P, P, P],
     "bk_chees_sums": [P, I, P, I, P, I, I, P],
     "bk_chees_stat": [P, I, P, I, P, I, P, P, P, P, P, P, P, I, I, P],
@@ -148,7 +151,8 @@ SIGNATURES = {
     "bk_host_exp": [F],
 }
 _RESTYPE = {"bk_gemm_chains_work_elems": c_int64, "bk_cov_k_chunk": c_int64, "bk_cov_accumulate_work_elems": c_int64, "bk_host_log1p": c_double, "bk_host_exp": c_double, "bk_refresh_work_elems": c_int64, "bk_sort_by_key_work_bytes": c_int64, "bk_resample_ordered_work_bytes": c_int64,
-             "bk_autocorr_fft_work_bytes": c_int64, "bk_ess_multi_work_bytes": c_int64, "bk_ess_lag_sums_max_half": c_int64}
+             "bk_autocorr_fft_work_bytes": c_int64, "bk_ess_multi_work_bytes": c_int64, "bk_ess_lag_sums_max_half": c_int64,
+             "bk_hist_lds_bins": c_int64, "bk_hist_slab_chains": c_int64}
 
 
 class BkHipError(RuntimeError):
@@ -950,6 +954,27 @@ class Ops:
         assert S.shape == (D, D) and s.numel() == D and (center is None or center.numel() == D)
         self._call("bk_cov_accumulate", ptr(X), _ld(X), C, D, ptr(center), ptr(S), _ld(S), ptr(s), ptr(work),
                    0 if work is None else work.numel(), self._s())
+
+    def hist_lds_bins(self):
+        """The largest bin count whose B + 3 slots fit one LDS window of hist_accumulate (the slab is then read once)."""
+        return int(self.lib.bk_hist_lds_bins())
+
+    def hist_slab_chains(self, C, D, B):
+        """Chains one workgroup of hist_accumulate covers in a call of that shape."""
+        return int(self.lib.bk_hist_slab_chains(int(C), int(D), int(B)))
+
+    def hist_accumulate(self, theta, lo, scale, B, counts):
+        """counts[d, slot] += the chains of theta[d, :] in `slot` (0 below, 1..B the bins, B + 1 above, B + 2 NaN) of the
+        grid t = (x - lo[d]) * scale[d]; theta [D, C] with contiguous chains and a row pitch of its own, counts int64
+        [D, >= B + 3] with a row pitch of its own (only the first B + 3 columns are touched).  bk_hist_accumulate."""
+        D, C = theta.shape
+        assert counts.dtype == torch.int64 and counts.dim() == 2 and counts.shape[0] == D and counts.shape[1] >= int(B) + 3
+        assert counts.shape[1] == 1 or counts.stride(1) == 1
+        assert lo.dtype == torch.float64 and scale.dtype == torch.float64 and lo.is_contiguous() and scale.is_contiguous()
+        assert lo.numel() == D and scale.numel() == D
+        ldc = counts.stride(0) if D > 1 else max(counts.stride(0), counts.shape[1])
+        self._call("bk_hist_accumulate", ptr(theta), _ld(theta), C, D, ptr(lo), ptr(scale), int(B), ptr(counts), ldc,
+                   self._s())
 
     def gemm_chains_work(self, R, K, C):
         """Split-K scratch for gemm_chains (a tensor of bk_gemm_chains_work_elems doubles, or None: no split)."""

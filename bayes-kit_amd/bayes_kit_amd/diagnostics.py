@@ -77,6 +77,22 @@ def rhat_from_moments(mean_dc, m2_dc, n: int, ops=None, group=None) -> np.ndarra
     return torch.sqrt((nf - 1.0) / nf + var_means / mean_var).cpu().numpy()
 
 
+def pooled_mean_from_moments(mean_dc, m2_dc, n: int, ops=None, group=None) -> torch.Tensor:
+    """Per-dimension mean of the draws of all chains of all ranks pooled (every chain holds n >= 1 draws, so it is the mean
+    of the per-chain means): the first pass of ``_cross_chain_moments``, one kernel + one all_gather.  A device tensor [D]."""
+    ops = _ops(ops)
+    D, C = mean_dc.shape
+    if n < 1:
+        raise ValueError("pooled_mean requires len(chain) >= 1 for every chain in chains")
+    part = torch.zeros(3 * D + 1, dtype=torch.float64, device=mean_dc.device)
+    ops.rhat_partials(mean_dc, m2_dc, max(int(n), 2), None, part)  # (the row sums of the means do not depend on n)
+    part[3 * D] = float(C)
+    tot = _gather_sum(part, group)
+    if float(tot[3 * D].item()) < 1:
+        raise ValueError("pooled_mean requires len(chains) >= 1, but len(chains) = 0")
+    return tot[0:D] / tot[3 * D:3 * D + 1]  # (divided as a TENSOR: the same doubles on every device)
+
+
 def pooled_variance_from_moments(mean_dc, m2_dc, n: int, ops=None, group=None) -> torch.Tensor:
     """Per-dimension variance of the draws of all chains of all ranks pooled, from the same moments and the same two
     passes as R-hat: (n-1)/n * mean_c(var_c) + var_c(mean_c), both ddof = 1.  A device tensor [D]."""
@@ -276,6 +292,10 @@ class RunningMoments:
         (n-1)/n * mean_c(var_c) + var_c(mean_c), both ddof = 1 (needs n >= 2 draws and >= 2 chains, as rhat)."""
         return pooled_variance_from_moments(self.mean, self.m2, self.n, self._ops, group).cpu().numpy()
 
+    def pooled_mean(self, group=None) -> np.ndarray:
+        """Per-dimension mean of all draws seen so far, pooled over the chains of all ranks (needs n >= 1 draws)."""
+        return pooled_mean_from_moments(self.mean, self.m2, self.n, self._ops, group).cpu().numpy()
+
     def reset(self) -> None:
         """Forget every draw: the moments start again from nothing."""
         self.mean.zero_()
@@ -383,6 +403,176 @@ class RunningCovariance:
         self.S.copy_(sd["S"].to(self.S.device))
         self.s.copy_(sd["s"].to(self.s.device))
         self.center.copy_(sd["center"].to(self.center.device))
+        self.n = int(sd["n"])
+
+
+def _named(idx) -> str:
+    """'coordinates [0, 3, 7]' for an error message, cut after eight."""
+    idx = [int(i) for i in idx]
+    return f"coordinate{'s' if len(idx) != 1 else ''} {idx[:8]}" + (f" and {len(idx) - 8} more" if len(idx) > 8 else "")
+
+
+class RunningHistogram:
+    """Streaming quantiles of EVERY coordinate in fixed memory: one fixed-grid histogram per coordinate, fed one draw at a
+    time (bk_hist_accumulate: one pass over the [D, C] draw) -- medians and credible intervals for runs whose draws cannot
+    be kept.  The state is ``D x (bins + 3)`` int64 counters, whatever the number of chains and draws.
+
+    Coordinate d has ``bins`` equal bins on ``[lo[d], hi[d])`` plus three slots: 0 "below", bins + 1 "above", bins + 2 NaN.
+    The slot of a value x is ``t = (x - lo) * scale`` (one rounded subtraction, one rounded multiplication, ``scale =
+    bins / (hi - lo)`` computed once on the host): NaN -> bins + 2, t < 0 -> 0, t >= bins -> bins + 1, else 1 + int(t).  The
+    counters are integers, so the counts are the same bits for every launch geometry and every split of the chains over
+    ranks, and a few lines of NumPy restate them exactly.
+
+    A quantile is read from the counts: the k-th smallest value, k = ceil(p n), lies in the first slot whose running count
+    reaches k, and is placed inside that bin by its rank among the bin's values.  It differs from the k-th order statistic
+    of everything fed by less than ONE bin width (both lie in the same bin); with ``from_moments`` at its defaults a bin is
+    1/32 of a posterior standard deviation.  Values off the grid are counted, never dropped: ``coverage()`` says how many
+    were on it, and a quantile that falls off the grid is -inf or +inf (with one warning)."""
+
+    def __init__(self, lo, hi, bins: int = 512, ops=None):
+        self._ops = _ops(ops)
+        dev = self._ops.device
+        lo_h, hi_h = (np.array(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v, dtype=np.float64).reshape(-1)
+                      for v in (lo, hi))
+        bins = int(bins)
+        if not 1 <= bins <= 65536:
+            raise ValueError(f"RunningHistogram requires 1 <= bins <= 65536, but bins = {bins}")
+        if lo_h.shape != hi_h.shape or lo_h.size < 1:
+            raise ValueError(f"RunningHistogram takes lo and hi of one length D >= 1, got {lo_h.size} and {hi_h.size}")
+        bad = np.flatnonzero(~(np.isfinite(lo_h) & np.isfinite(hi_h)))
+        if bad.size:
+            raise ValueError(f"RunningHistogram requires finite edges: lo or hi is not finite at {_named(bad)}")
+        bad = np.flatnonzero(hi_h <= lo_h)
+        if bad.size:
+            raise ValueError(f"RunningHistogram requires lo < hi: hi <= lo at {_named(bad)}")
+        with np.errstate(over="ignore", divide="ignore"):
+            scale_h = float(bins) / (hi_h - lo_h)
+        bad = np.flatnonzero(~np.isfinite(scale_h) | (scale_h <= 0.0))
+        if bad.size:
+            raise ValueError(f"RunningHistogram: bins / (hi - lo) is not a finite positive number at {_named(bad)}")
+        self.bins = bins
+        self._lo_h, self._hi_h, self._scale_h = lo_h, hi_h, scale_h
+        self.lo = torch.from_numpy(lo_h).to(dev)
+        self.scale = torch.from_numpy(scale_h).to(dev)
+        self._counts = torch.zeros((lo_h.size, bins + 3), dtype=torch.int64, device=dev)
+        self.n = 0
+
+    @classmethod
+    def from_moments(cls, moments: "RunningMoments", bins: int = 512, width: float = 8.0, group=None):
+        """The grid ``pooled mean -/+ width * sqrt(pooled variance)`` of a RunningMoments fed during warmup (over the chains
+        of all ranks of ``group``: every rank gets the same grid).  At the defaults a bin is 1/32 of a posterior sd."""
+        width = float(width)
+        if not (np.isfinite(width) and width > 0.0):
+            raise ValueError(f"from_moments requires a finite width > 0, but width = {width}")
+        mean = moments.pooled_mean(group)
+        var = moments.pooled_variance(group)
+        bad = np.flatnonzero(~(np.isfinite(var) & (var > 0.0) & np.isfinite(mean)))
+        if bad.size:
+            raise ValueError(f"from_moments requires a finite mean and a finite variance > 0: not so at {_named(bad)}")
+        half = width * np.sqrt(var)
+        return cls(mean - half, mean + half, bins=bins, ops=moments._ops)
+
+    @property
+    def D(self) -> int:
+        return self._counts.shape[0]
+
+    def update(self, theta, layout=None) -> None:
+        """theta: the sampler's draw, the engine's [D, C] buffer or the (C, D) view returned by ``sample()`` (as
+        RunningMoments.update; C may differ between updates).  n += C."""
+        D = self.D
+        if theta.dim() != 2:
+            raise ValueError(f"expected a 2-D draw, got shape {tuple(theta.shape)}")
+        if layout is None:  # (the chain count is whichever extent is not D; a square draw is told apart by _as_dc)
+            C = theta.shape[1] if (theta.shape[0] == D and theta.shape[1] != D) else theta.shape[0]
+        else:
+            C = theta.shape[1] if layout == "dc" else theta.shape[0]
+        t = _as_dc(theta, D, C, layout)
+        if (t.shape[1] > 1 and t.stride(1) != 1) or t.dtype != torch.float64:
+            t = t.to(torch.float64).contiguous()
+        self._ops.hist_accumulate(t, self.lo, self.scale, self.bins, self._counts)
+        self.n += C
+
+    # -- read-outs ---------------------------------------------------------------------------------------------------------
+    def counts(self, group=None) -> torch.Tensor:
+        """int64 [D, bins + 3], summed over the ranks of ``group`` (one all_gather; integer sums have no order)."""
+        return _gather_sum(self._counts, group).clone()
+
+    def edges(self) -> np.ndarray:
+        """[D, bins + 1]: edge b of coordinate d is lo[d] + b / scale[d] (bin b is [edge b, edge b + 1))."""
+        return self._lo_h[:, None] + np.arange(self.bins + 1, dtype=np.float64)[None, :] / self._scale_h[:, None]
+
+    def _host_counts(self, group):
+        return _gather_sum(self._counts, group).cpu().numpy()
+
+    def coverage(self, group=None) -> np.ndarray:
+        """[D]: the fraction of the non-NaN values of each coordinate inside [lo, hi) (NaN where there is none)."""
+        c = self._host_counts(group)
+        B = self.bins
+        inside, n = c[:, 1:B + 1].sum(axis=1), c[:, :B + 2].sum(axis=1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(n > 0, inside / np.maximum(n, 1), np.nan)
+
+    def quantile(self, probs, group=None) -> np.ndarray:
+        """[len(probs), D] float64.  Per coordinate, with n the number of non-NaN values and c the counts: k = min(max(
+        ceil(p n), 1), n); b = the first slot whose running count cum[b] reaches k; slot 0 -> -inf, slot bins + 1 -> +inf
+        (one RuntimeWarning), else lo + ((b - 1) + (k - cum[b - 1] - 0.5) / c[b]) / scale.  n == 0 -> NaN."""
+        p = np.atleast_1d(np.asarray(probs, dtype=np.float64))
+        if p.ndim != 1 or not np.all((p >= 0.0) & (p <= 1.0)):
+            raise ValueError("quantile requires probabilities in [0, 1]")
+        B = self.bins
+        c = self._host_counts(group)[:, :B + 2]
+        cum = np.cumsum(c, axis=1)
+        n = cum[:, -1]
+        rows = np.arange(c.shape[0])
+        out = np.full((p.size, c.shape[0]), np.nan)
+        off = np.zeros(c.shape[0], dtype=bool)
+        for i, pi in enumerate(p):
+            k = np.minimum(np.maximum(np.ceil(pi * n.astype(np.float64)).astype(np.int64), 1), n)
+            b = (cum < k[:, None]).sum(axis=1)  # the first slot with cum >= k (n == 0: meaningless, masked below)
+            b = np.minimum(b, B + 1)
+            before = np.where(b > 0, cum[rows, np.maximum(b - 1, 0)], 0)
+            cb = np.maximum(c[rows, b], 1)
+            q = self._lo_h + ((b - 1) + (k - before - 0.5) / cb) / self._scale_h
+            q = np.where(b == 0, -np.inf, np.where(b == B + 1, np.inf, q))
+            out[i] = np.where(n > 0, q, np.nan)
+            off |= (n > 0) & ((b == 0) | (b == B + 1))
+        if off.any():
+            import warnings
+
+            warnings.warn(f"RunningHistogram.quantile: a requested quantile of {int(off.sum())} of {off.size} coordinates "
+                          "lies off the grid (-inf / +inf returned; see coverage())", RuntimeWarning, stacklevel=2)
+        return out
+
+    def median(self, group=None) -> np.ndarray:
+        return self.quantile([0.5], group)[0]
+
+    def interval(self, mass: float = 0.9, group=None):
+        """The equal-tailed interval of probability ``mass``: (lower, upper), [D] each."""
+        mass = float(mass)
+        if not 0.0 < mass < 1.0:
+            raise ValueError(f"interval requires 0 < mass < 1, but mass = {mass}")
+        q = self.quantile([0.5 * (1.0 - mass), 1.0 - 0.5 * (1.0 - mass)], group)
+        return q[0], q[1]
+
+    def reset(self) -> None:
+        """Forget every draw; the grid stays."""
+        self._counts.zero_()
+        self.n = 0
+
+    # checkpoint / resume: the grid, the bin count, n and the counts; restored, the updates continue to the same integers
+    def state_dict(self):
+        return {"lo": torch.from_numpy(self._lo_h.copy()), "hi": torch.from_numpy(self._hi_h.copy()), "bins": self.bins,
+                "n": self.n, "counts": self._counts.detach().cpu().clone()}
+
+    def load_state_dict(self, sd):
+        lo, hi = np.asarray(sd["lo"], dtype=np.float64), np.asarray(sd["hi"], dtype=np.float64)
+        if int(sd["bins"]) != self.bins or lo.shape != self._lo_h.shape or not (
+                np.array_equal(lo, self._lo_h) and np.array_equal(hi, self._hi_h)):
+            raise ValueError("checkpoint holds a histogram on another grid (lo, hi and bins must equal this one's)")
+        if tuple(sd["counts"].shape) != tuple(self._counts.shape):
+            raise ValueError(f"checkpoint holds counts of shape {tuple(sd['counts'].shape)}, expected "
+                             f"{tuple(self._counts.shape)}")
+        self._counts.copy_(sd["counts"].to(self._counts.device))
         self.n = int(sd["n"])
 
 

@@ -1019,6 +1019,31 @@ int bk_rhat_partials(const double* mean, const double* m2, int64_t ld, int64_t n
 int bk_superchain_moments(const double* mean, const double* m2, int64_t ld, int64_t n, int64_t M, double* s_out,
                           double* w_out, int64_t ldk, int64_t C, int64_t D, void* stream);
 
+/* Fixed-grid histograms of every coordinate of a draw (RunningHistogram): counts[d][slot] += the number of chains c whose
+ * theta[d][c] falls into `slot`, for theta [D][ld] and counts [D][ldc] int64, ldc >= B + 3.  Row d has B + 3 slots:
+ *     0         below the grid            1 .. B    the bins            B + 1    above the grid            B + 2    NaN
+ * The slot of x is decided by ONE rule, which is the contract (it is what lets NumPy restate the counts bit for bit):
+ *     x != x                  -> B + 2
+ *     t = (x - lo[d]) * scale[d]          one rounded fp64 subtraction, then one rounded fp64 multiplication
+ *     t < 0                   -> 0        (-inf; not x == lo and not t == -0.0: those are bin 0)
+ *     t >= B                  -> B + 1    (+inf, a product that overflows, x == hi on a dyadic grid: the range is half-open)
+ *     otherwise               -> 1 + (int64)t
+ * x * scale - lo * scale, fused or not, is a different function, and so is a comparison against precomputed edges.
+ * lo and scale are device doubles [D]; the caller has made sure that they are finite and scale > 0.  1 <= B <= 65,536.
+ * The call ADDS to counts and touches only slots 0 .. B + 2 of each of the D rows (never the padding up to ldc).  ld may be
+ * odd: rows need not start on 16 bytes.
+ * One workgroup per (row, slab of bk_hist_slab_chains(C, D, B) chains) counts in a private LDS histogram of 32-bit counters
+ * (a slab is at most 2^30 chains) and adds its non-zero counters to counts with 64-bit integer atomics: integer sums, so
+ * the result is the same bits for every slab size, launch geometry and arrival order.  Up to bk_hist_lds_bins() bins all
+ * slots fit one LDS window and the slab is read once; above, the same kernel walks the slots window by window and reads
+ * its slab once per window.  HBM traffic 8*C*D bytes plus the touched counters.
+ * BK_E_ARG: a NULL pointer, C < 0, D < 0, B < 1, B > 65,536, ld < C, ldc < B + 3, more than 65,535 slabs; decided before
+ * any HIP call.  C == 0 or D == 0: BK_OK, nothing launched.  bk_hist_slab_chains returns 0 for arguments without a launch. */
+int64_t bk_hist_lds_bins(void);
+int64_t bk_hist_slab_chains(int64_t C, int64_t D, int64_t B);
+int bk_hist_accumulate(const double* theta, int64_t ld, int64_t C, int64_t D, const double* lo, const double* scale,
+                       int64_t B, int64_t* counts, int64_t ldc, void* stream);
+
 /* The acceptance statistic a step-size adaptation averages, before the accept test overwrites lp_cur:
  *     d_c    = (lp_prop[c] - a_prop[c]) - (lp_cur[c] - a_cur[c])      the h1 - h0 of bk_mh_accept in HMC mode
  *     out[0] = sum_c min(1, bk_exp(min(0, d_c)))   over the chains whose d_c is not NaN
