@@ -76,6 +76,7 @@ SIGNATURES = {
     "bk_mala_propose_from_normals": [P, P, P, I, I, P, I, F, F, I, I, P],
     "bk_mala_propose_from_normals_precond": [P, P, P, I, I, P, P, I, F, F, I, I, P],
     "bk_normals_chain_major": [c_int, P, I, P, I, I, I, P, I, P],
+    "bk_normals_lanes_per_chain": [I, I],
     "bk_mala_logq": [P, P, P, P, I, F, P, P, I, I, P],
     "bk_mala_logq_precond": [P, P, P, P, I, P, F, P, P, I, I, P],
     "bk_mala_single_draw": [c_int, P, I, P, P, P, P, P, P, P, I, P, P, F, F, I, c_int, F, P],
@@ -727,6 +728,11 @@ class Ops:
         assert snapshot is None or (snapshot.shape == state.shape and snapshot.stride(0) == state.stride(0))
         self._call("bk_normals_chain_major", kind, ptr(state), state.stride(0), ptr(zt), zt.stride(0), C, D,
                    ptr(snapshot), int(max_workgroups or 0), self._s())
+
+    def normals_lanes_per_chain(self, C, D):
+        """Lanes per chain (16, 32 or 64) of the word-parallel generator's launch for C chains x D normals: its window is
+        4 x that many stream words per pass."""
+        return int(self.lib.bk_normals_lanes_per_chain(int(C), int(D)))
 
     def mala_logq(self, theta, grad, theta_prop, grad_prop, eps, lp_forward, lp_reverse):
         D, C = theta.shape

@@ -1182,6 +1182,8 @@ int bk_normals_chain_major(int rng_kind, uint64_t* state, int64_t ldr, double* z
   BK_RETURN_LAUNCH_STATUS();
 }
 
+int bk_normals_lanes_per_chain(int64_t C, int64_t D) { return (C < 1 || D < 1) ? 0 : zp_lanes_per_chain(C, D); }
+
 // ---- host self-test hooks: same source, host compilation ----------------------------
 static void host_tables(const double** wi, const double** fi) {
   static double s_wi[256], s_fi[256];

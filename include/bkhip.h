@@ -561,6 +561,12 @@ int bk_mala_propose_from_normals_precond(const double* theta, const double* grad
 int bk_normals_chain_major(int rng_kind, uint64_t* state, int64_t ldr, double* zt, int64_t ldz, int64_t C,
                            int64_t D, uint64_t* snapshot, int64_t max_workgroups, void* stream);
 
+/* Lanes of a wavefront per chain (16, 32 or 64) that the word-parallel generator uses for a launch of C chains x D
+ * normals -- bk_normals_chain_major and every entry point that takes the same path (bk_momentum_refresh with scratch,
+ * bk_momentum_refresh_precond, bk_dr_refresh_begin): a pass evaluates a window of 4 x lanes stream words per chain.
+ * A function of (C, D) only; launches nothing.  0 for C < 1 or D < 1. */
+int bk_normals_lanes_per_chain(int64_t C, int64_t D);
+
 /* ONE chain driven by a host model (the reference's own call shape, README.md:13-32; mala.py:40-66): everything of a
  * draw that follows the model call, and the next draw's proposal, in ONE launch of one lane.
  *   have_prop != 0: host_in[0] = log density at theta_prop, host_in[1 .. D] = its gradient (written by the caller

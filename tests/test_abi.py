@@ -166,6 +166,10 @@ def test_error_behaviour_of_the_c_abi_without_a_gpu():
     assert lib.bk_mala_logq(p, p, p, p, 3, 0.1, p, p, 4, 8, None) == E_ALIGN
     assert lib.bk_mala_propose_from_normals(p, p, p, 5, 3, p, 4, 0.1, 0.2, 4, 8, None) == E_ALIGN  # z strides
     assert lib.bk_refresh_work_elems(5, 33) == 5 * 40
+    # the generator's launch rule, asked without a launch: 16, 32 or 64 lanes per chain; 0 for an empty problem
+    assert [lib.bk_normals_lanes_per_chain(70, D) for D in (57, 58, 120, 121)] == [16, 32, 32, 64]
+    assert lib.bk_normals_lanes_per_chain(65536, 1024) in (16, 32, 64)
+    assert lib.bk_normals_lanes_per_chain(0, 8) == 0 and lib.bk_normals_lanes_per_chain(8, 0) == 0
 
 
 def test_fft_plan_of_the_reference_call_shape_is_not_padded_to_a_wide_batch():
