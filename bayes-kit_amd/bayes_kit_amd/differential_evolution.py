@@ -14,9 +14,11 @@ to ``theta_j2``: in the other mode, if the two sit in different ones.  ``jump_ev
 a mode-jumping draw (ter Braak's ``gamma = 1`` step); all other draws use ``gamma``, by default ``2.38 / sqrt(2 D)``.
 
 The column layout, the caches, the accept step, the column select, the streams and the checkpoints are ``Stretcher``'s; only
-``_propose`` differs.  Each active walker draws from ITS OWN stream, in this order: uniform ``u_1``, uniform ``u_2``, one
-standard normal (``Generator.standard_normal()``, bit for bit: ``bk_momentum_refresh`` on one masked row), the accept
-uniform; inactive walkers draw nothing.  The proposal is the ``bk_de_propose`` kernel (include/bkhip.h).
+``_propose`` differs; the tempered one takes its ladder (swap rounds, statistics, the ladder's share of a checkpoint) from
+``TemperedStretcher``, that is from ``tempering.ReplicaLadder``, unchanged.  Each active walker draws from ITS OWN stream,
+in this order: uniform ``u_1``, uniform ``u_2``, one standard normal (``Generator.standard_normal()``, bit for bit:
+``bk_momentum_refresh`` on one masked row), the accept uniform; inactive walkers draw nothing.  The proposal is the
+``bk_de_propose`` kernel (include/bkhip.h).
 
 ``sigma`` perturbs the SCALAR ``gamma`` only, so the moves of a walker stay inside the span of the other half's
 differences: with ``H = walkers / 2 <= D`` that span has fewer than ``D`` directions and the sampler is not ergodic.  The
@@ -85,14 +87,10 @@ class _DEMove:
                        self._gamma0(), self._sigma, self._theta_p[:, act], self._partners[0, act], self._partners[1, act],
                        self._gamma_used[act])
 
-    def _de_extra(self):
-        return {"gamma": self._gamma, "sigma": self._sigma, "jump_every": self._jump_every, "walkers": self._walkers,
-                "ensembles": self._ensembles}
-
-    def _load_extra(self, extra):
-        mine = self._state_extra()
-        if extra and any(extra.get(k, v) != v for k, v in mine.items()):
-            raise ValueError(f"checkpoint is for a {type(self).__name__} with {extra}, this one has {mine}")
+    def _state_extra(self):
+        extra = super()._state_extra()
+        del extra["a"]  # (the stretch bound is not a setting of this move)
+        return dict(gamma=self._gamma, sigma=self._sigma, jump_every=self._jump_every, **extra)
 
     @property
     def gamma(self) -> float:
@@ -133,9 +131,6 @@ class DifferentialEvolution(_DEMove, Stretcher):
         Stretcher.__init__(self, model, 2.0, walkers, init, seed=seed, ensembles=ensembles, chain_id0=chain_id0, ops=ops)
         self._de_buffers()
 
-    def _state_extra(self):
-        return self._de_extra()
-
 
 class TemperedDifferentialEvolution(_DEMove, TemperedStretcher):
     """``TemperedStretcher``'s ladder, tempered accept test, swap rounds and statistics on the differential-evolution
@@ -149,8 +144,3 @@ class TemperedDifferentialEvolution(_DEMove, TemperedStretcher):
         TemperedStretcher.__init__(self, model, betas, 2.0, walkers, init, seed=seed, replicas=replicas,
                                    swap_every=swap_every, chain_id0=chain_id0, ops=ops)
         self._de_buffers()
-
-    def _state_extra(self):
-        extra = self._de_extra()
-        extra.update(betas=[float(b) for b in self._betas], replicas=self._replicas, swap_every=self._swap_every)
-        return extra

@@ -15,7 +15,9 @@ stream (``numpy.random.Philox(key=[seed, chain_id0 + column])``), in the order `
 (accept); inactive walkers draw nothing, so after ``n`` draws every stream stands ``3 n`` uniforms further.  The proposal is
 the ``bk_stretch_propose`` kernel (include/bkhip.h).  The log density of every walker is cached (the reference's
 ``TODO(carpenter)``).  ``tempering.TemperedStretcher`` runs the same draw on a ladder of tempered targets: it overrides the
-accept step, the end of a draw and the cached density (``_accept``, ``_end_draw``, ``_init_cache``, ``_logp_out``);
+accept step, the end of a draw and the cached density (``_accept``, ``_end_draw``, ``_init_cache``, ``_logp_out``), and
+``tempering.ReplicaLadder``, mixed in before this class, the checkpoint's content and the acceptance read-out
+(``_state_tensors``, ``_state_extra``, ``load_state_dict``, ``accept_rate``);
 ``differential_evolution.DifferentialEvolution`` runs another move in the same two half-updates: it overrides the draws and
 the proposal of one half-update (``_propose``).
 """
@@ -127,7 +129,7 @@ class Stretcher(ManyChainSampler):
     def _load_extra(self, extra):
         mine = self._state_extra()
         if extra and any(extra.get(k, v) != v for k, v in mine.items()):
-            raise ValueError(f"checkpoint is for a Stretcher with {extra}, this one has {mine}")
+            raise ValueError(f"checkpoint is for a {type(self).__name__} with {extra}, this one has {mine}")
 
     @property
     def walkers(self) -> int:

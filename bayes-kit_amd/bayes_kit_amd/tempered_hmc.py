@@ -8,6 +8,11 @@ the likelihood, ``beta = 0`` is allowed and the ladder yields the evidence.  Any
 engine's gradient bridge (``bk_eval``, ``bk_gradient``, ``log_density_gradient``): the whole log density is tempered, ``lp0``
 is absent and every ``beta`` must be positive.
 
+The ladder itself is ``tempering.ReplicaLadder``'s, shared with ``TemperedStretcher``: the check of ``betas``, ``replicas`` and
+``swap_every``, the per-column tables, the swap round, the statistics and their read-outs, the index helpers and the
+ladder's share of a checkpoint.  This module keeps what is HMC's: the step size of every rung, the cached gradients (which
+it exchanges after a swap round), the draw and ``warmup()``.
+
 Layout: ``C = replicas * T * chains`` columns, column ``c = (r * T + t) * H + i`` for chain ``i`` of rung ``t`` of replica
 ``r`` (``H = chains``, the rung fastest), so rungs ``t`` and ``t + 1`` of a replica are columns ``c`` and ``c + H``: the two
 adjacent slices ``bk_replica_swap`` exchanges.  Every column carries its inverse temperature and its step size (and half of
@@ -30,52 +35,38 @@ step sizes from their own replicas, and nothing is exchanged between them.
 """
 from __future__ import annotations
 
-import math
-
 import numpy as np
 import torch
 
 from . import _lib
 from ._engine import ManyChainSampler
 from .adapt import DualAveraging
-from .tempering import _positive_int
+from .tempering import ReplicaLadder, _positive_int
 
 
-class TemperedHMC(ManyChainSampler):
+class TemperedHMC(ReplicaLadder, ManyChainSampler):
     """``betas``: strictly decreasing, finite, >= 0 (0 only for a split model); ``stepsize``: a scalar or one entry per rung;
     ``steps``: leapfrog steps (>= 1); ``chains``: chains per rung; ``replicas``: independent ladders side by side (whole
     replicas per rank: shard with ``chain_id0``); ``swap_every``: draws between swap rounds; ``init``: (replicas * T * chains,
     D).  ``sample()`` returns every chain's ``theta`` after the swap round and its UNTEMPERED log density; ``cold_rows()`` are
     the rows that sample the target itself (rung 0)."""
 
+    _SPLIT_METHODS = ("log_prior_gradient", "log_likelihood_gradient")
+
     def __init__(self, model, betas, stepsize, steps, metric_diag=None, init=None, *, seed=None, chains=None,
                  replicas: int = 1, swap_every: int = 1, chain_id0: int = 0, ops=None):
         if getattr(model, "batched", False) is not True:
             raise ValueError("TemperedHMC needs a batched device model")
-        b = np.asarray(betas, dtype=np.float64)
-        if b.ndim != 1 or b.shape[0] < 1 or not np.isfinite(b).all() or (b < 0.0).any() or (np.diff(b) >= 0.0).any():
-            raise ValueError(f"betas must be a strictly decreasing sequence of finite values >= 0; found {betas=}")
-        if not _positive_int(replicas):
-            raise ValueError(f"replicas must be a strictly positive integer; found {replicas=}")
-        if not _positive_int(swap_every):
-            raise ValueError(f"swap_every must be a strictly positive integer; found {swap_every=}")
+        self._ladder_args(model, betas, replicas, swap_every)
         if not _positive_int(steps):
             raise ValueError(f"steps must be a strictly positive integer; found {steps=}")
-        T = int(b.shape[0])
-        if chains is None and init is not None and np.ndim(init) == 2 and np.shape(init)[0] % (int(replicas) * T) == 0:
-            chains = int(np.shape(init)[0]) // (int(replicas) * T)
+        E = self._replicas * self._T
+        if chains is None and init is not None and np.ndim(init) == 2 and np.shape(init)[0] % E == 0:
+            chains = int(np.shape(init)[0]) // E
         if not _positive_int(chains):
             raise ValueError(f"chains (per rung) must be a strictly positive integer; found {chains=}")
-        self._split = (callable(getattr(model, "log_prior_gradient", None))
-                       and callable(getattr(model, "log_likelihood_gradient", None)))
-        if not self._split and b[-1] <= 0.0:
-            raise ValueError("beta = 0 needs a batched model with log_prior_gradient and log_likelihood_gradient: without "
-                             "that split the whole log density is tempered and every beta must be > 0")
-        self._betas = b
-        self._T, self._replicas, self._swap_every = T, int(replicas), int(swap_every)
         self._H, self._steps = int(chains), int(steps)
-        self._E = self._replicas * T
-        C, D = self._E * self._H, int(model.dims())
+        C, D = E * self._H, int(model.dims())
         eps = self._check_stepsizes(stepsize)
         if init is not None and tuple(np.shape(init)) != (C, D):
             raise ValueError(f"init must be shape of draw {(C, D)}; found {tuple(np.shape(init))}")
@@ -93,28 +84,10 @@ class TemperedHMC(ManyChainSampler):
         self._lp0_p = torch.zeros(C, **f64) if self._split else None
         self._kin0, self._kin1, self._logu = (torch.zeros(C, **f64) for _ in range(3))
         self._mask = torch.zeros(C, dtype=torch.uint8, device=dev)
-        self._swapped = torch.zeros(C, dtype=torch.uint8, device=dev)
-        self._swap_ran = False
-        rung = self.rung_index()
-        self._rung_host = rung.cpu().numpy()
-        self._beta_col = torch.as_tensor(b, **f64)[rung].contiguous()
+        self._init_ladder(self._H, 1)
+        self._rung_host = self.rung_index().cpu().numpy()
         self._eps_col, self._half_col, self._neg_half_col = (torch.zeros(C, **f64) for _ in range(3))
         self._install_stepsizes(eps)
-        self._lower = []  # per parity: the chains on the lower rung index of a pair (they draw the swap's uniform)
-        for p in (0, 1):
-            low = ((rung % 2 == p) & (rung + 1 < T)).to(torch.uint8).contiguous()
-            self._lower.append(low if bool(low.any()) else None)
-        # statistics, all on the device; block e = r * T + t of H columns is rung t of replica r
-        E = self._E
-        self._rung_acc = torch.zeros(E, dtype=torch.int32, device=dev)
-        self._swap_prop = torch.zeros(E, dtype=torch.int32, device=dev)
-        self._swap_acc = torch.zeros(E, dtype=torch.int32, device=dev)
-        self._ll_sum = torch.zeros(E, **f64)
-        self._lse = torch.full((E,), -math.inf, **f64)
-        self._stat_n = torch.zeros(1, dtype=torch.int64)  # (host: draws the statistics cover)
-        # (beta_{t-1} - beta_t) of every block's rung t; 0.0 for rung 0, whose entry of `_lse` is never read
-        db = np.concatenate([[0.0], b[:-1] - b[1:]])
-        self._dbeta_e = torch.as_tensor(np.tile(db, self._replicas), **f64)
         self._draws = 0
         self._grad_parts(self._theta_dc, self._g_ll, self._g_lp0, self._ll, self._lp0)
 
@@ -194,30 +167,13 @@ class TemperedHMC(ManyChainSampler):
         if self._split:
             ops.select_columns(self._mask, self._g_lp0, self._gp_lp0)
         self._draws += 1
-        self._swap_ran = False
-        if self._draws % self._swap_every == 0:
-            low = self._lower[(self._draws // self._swap_every) % 2]
-            if low is not None:
-                ops.log_uniform(self._rng_kind, self._rng_state, self._logu, low)
-                # the state and the copy of it that this draw returns change places alike; the decision overwrites ll, so the
-                # cached gradients follow by the exchange pass alone
-                ops.replica_swap(th, out, self._ll, self._lp0, beta, self._logu, low, self._swapped, self._swap_prop,
-                                 self._swap_acc, H)
-                ops.exchange_columns(self._g_ll, self._swapped, H)
-                if self._split:
-                    ops.exchange_columns(self._g_lp0, self._swapped, H)
-                self._swap_ran = True
+        if self._swap_round(out):  # (the decision overwrote ll: the cached gradients follow by the exchange pass alone)
+            ops.exchange_columns(self._g_ll, self._swapped, H)
+            if self._split:
+                ops.exchange_columns(self._g_lp0, self._swapped, H)
         self._accumulate()
         self._out = out
         return self._draw_out(th, self._lp0 + self._ll if self._split else self._ll)
-
-    def _accumulate(self):
-        """This draw's share of the running statistics: per block the sum of ll, and the log-sum-exp of
-        (beta_{t-1} - beta_t) ll over the chains of rung t (the stepping stone from rung t to rung t - 1)."""
-        ll = self._ll.view(self._E, self._H)
-        self._ll_sum += ll.sum(dim=1)
-        torch.logaddexp(self._lse, torch.logsumexp(ll * self._dbeta_e[:, None], dim=1), out=self._lse)
-        self._stat_n += 1
 
     # -- warmup: one step size per rung ------------------------------------------------------------------------------------
     def warmup(self, draws, target_accept=0.8):
@@ -248,46 +204,29 @@ class TemperedHMC(ManyChainSampler):
 
     # -- state -------------------------------------------------------------------------------------------------------------
     def _state_tensors(self):
-        st = {"theta": self._theta_dc, "ll": self._ll, "grad_ll": self._g_ll, "rung_accepted": self._rung_acc,
-              "swap_proposed": self._swap_prop, "swap_accepted": self._swap_acc, "ll_sum": self._ll_sum, "lse": self._lse,
-              "stat_draws": self._stat_n}
+        st = super()._state_tensors()
+        st["grad_ll"] = self._g_ll
         if self._split:
-            st["lp0"] = self._lp0
             st["grad_lp0"] = self._g_lp0
         return st
 
-    def _ladder(self):
-        return {"betas": [float(b) for b in self._betas], "chains_per_rung": self._H, "replicas": self._replicas,
-                "swap_every": self._swap_every, "steps": self._steps, "split": self._split}
-
     def _state_extra(self):
-        return dict(self._ladder(), stepsizes=[float(e) for e in self._eps])
+        return dict(super()._state_extra(), chains_per_rung=self._H, steps=self._steps, split=self._split,
+                    stepsizes=[float(e) for e in self._eps])
 
-    def _check_ladder(self, extra):
-        mine = self._ladder()
+    def _load_extra(self, extra):
+        """Refuses a checkpoint of other settings than this sampler's; the step sizes are the checkpoint's own."""
+        mine = self._state_extra()
+        del mine["stepsizes"]
         if any(extra.get(k) != v for k, v in mine.items()):
             raise ValueError(f"checkpoint is for a TemperedHMC with {extra}, this one has {mine}")
-        return self._check_stepsizes(extra["stepsizes"])
+        self._check_stepsizes(extra["stepsizes"])
 
     def load_state_dict(self, sd):
-        eps = self._check_ladder(sd["meta"].get("extra", {}))  # another ladder is refused before anything is overwritten
-        super().load_state_dict(sd)
-        self._install_stepsizes(eps)
-        self._swap_ran = False
+        super().load_state_dict(sd)  # (`_load_extra` first: another ladder is refused before anything is overwritten)
+        self._install_stepsizes(self._check_stepsizes(sd["meta"]["extra"]["stepsizes"]))
 
     # -- surface -----------------------------------------------------------------------------------------------------------
-    @property
-    def betas(self) -> np.ndarray:
-        return self._betas.copy()
-
-    @property
-    def replicas(self) -> int:
-        return self._replicas
-
-    @property
-    def swap_every(self) -> int:
-        return self._swap_every
-
     @property
     def steps(self) -> int:
         return self._steps
@@ -299,74 +238,3 @@ class TemperedHMC(ManyChainSampler):
     @property
     def last_accept(self):
         return self._mask.bool()
-
-    @property
-    def last_swapped(self):
-        """Whether a chain changed places with chain i of the next rung in the last draw's swap round (bool, length C; set
-        at the chain on the lower rung index of the pair)."""
-        return self._swapped.bool() if self._swap_ran else torch.zeros_like(self._swapped).bool()
-
-    def _block_index(self):
-        return torch.arange(self._C, dtype=torch.int64, device=self._ops.device) // self._H
-
-    def rung_index(self):
-        """The rung of every row of a draw (length C): block e = r * T + t of H rows is rung t of replica r."""
-        return self._block_index() % self._T
-
-    def replica_index(self):
-        """The replica of every row of a draw (length C)."""
-        return self._block_index() // self._T
-
-    def cold_rows(self):
-        """The rows of a draw on rung 0: the chains that sample the target at betas[0]."""
-        return torch.nonzero(self.rung_index() == 0).reshape(-1)
-
-    # -- statistics: read only when asked ----------------------------------------------------------------------------------
-    def _stat_draws(self) -> int:
-        return int(self._stat_n.item())
-
-    def reset_statistics(self):
-        """Forget the counters and the running statistics gathered so far (a burn-in)."""
-        for t in (self._rung_acc, self._swap_prop, self._swap_acc, self._ll_sum, self._stat_n):
-            t.zero_()
-        self._lse.fill_(-math.inf)
-
-    def accept_rate(self) -> float:
-        n = self._stat_draws() * self._C
-        return float(self._rung_acc.sum().item()) / n if n else float("nan")
-
-    def rung_accept_rate(self) -> np.ndarray:
-        """Accepted proposals per draw and chain, per rung -> [T]."""
-        n = self._stat_draws() * self._replicas * self._H
-        acc = self._rung_acc.view(self._replicas, self._T).sum(dim=0).cpu().numpy().astype(np.float64)
-        return acc / n if n else np.full(self._T, np.nan)
-
-    def swap_rate(self) -> np.ndarray:
-        """Accepted swaps per proposed one, per pair (t, t + 1) -> [T - 1] (NaN for a pair that never proposed)."""
-        shape = (self._replicas, self._T)
-        prop = self._swap_prop.view(shape).sum(dim=0).cpu().numpy().astype(np.float64)[:self._T - 1]
-        acc = self._swap_acc.view(shape).sum(dim=0).cpu().numpy().astype(np.float64)[:self._T - 1]
-        with np.errstate(invalid="ignore", divide="ignore"):
-            return np.where(prop > 0, acc / prop, np.nan)
-
-    def mean_log_likelihood(self) -> np.ndarray:
-        """The mean of ll over the chains of every rung and the draws since the last reset -> [replicas, T] (the integrand
-        of thermodynamic integration)."""
-        n = self._stat_draws() * self._H
-        s = self._ll_sum.view(self._replicas, self._T).cpu().numpy()
-        return s / n if n else np.full(s.shape, np.nan)
-
-    def log_evidence(self) -> np.ndarray:
-        """The stepping-stone estimate of the log evidence, sum_t log mean_{rung t+1} exp((beta_t - beta_{t+1}) ll), per
-        replica -> [replicas].  Needs the prior / likelihood split and a ladder from 1 down to 0."""
-        if not self._split:
-            raise ValueError("log_evidence needs a model with the prior / likelihood split: the base measure of a tempered "
-                             "log_density is improper")
-        if self._betas[0] != 1.0 or self._betas[-1] != 0.0:
-            raise ValueError(f"log_evidence needs betas[0] == 1 and betas[-1] == 0; found {self._betas[0]} and "
-                             f"{self._betas[-1]}")
-        n = self._stat_draws() * self._H
-        if not n:
-            return np.full(self._replicas, np.nan)
-        lse = self._lse.view(self._replicas, self._T).cpu().numpy()
-        return (lse[:, 1:] - math.log(n)).sum(axis=1)
