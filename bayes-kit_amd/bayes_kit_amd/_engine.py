@@ -125,6 +125,93 @@ def numpy_generator_from_words(kind: int, w: np.ndarray) -> np.random.Generator:
 
 
 # ---------------------------------------------------------------------------------------
+# randomness generated one draw ahead (prefetch_rng)
+# ---------------------------------------------------------------------------------------
+class LookAhead:
+    """The side stream on which a sampler generates the NEXT draw's randomness, into the other of two buffer slots, while
+    this draw's kernels run on the main stream.  It knows slots, streams and events; the sampler owns the buffers, says which
+    kernels generate (`generate(slot)`, handed to take() and start_next(): kept here it would tie sampler and owner into a
+    reference cycle, and __del__'s drain would wait for the garbage collector) and where the logical stream position lies.
+
+    Events are created ONCE per sampler and re-recorded every draw.  Creating two torch.cuda.Event
+    objects per draw and dropping them while GPU-side waits on them were still pending corrupted the
+    host heap under the randomised soak (glibc "malloc(): invalid size", a chain off by one ulp) --
+    about once per 100,000 short-lived samplers, more often the more events a draw used
+    (tensor.record_stream() made it frequent).  With persistent events, a GPU-side join at the end of
+    every draw and a drained side stream before the sampler's buffers are released, it is gone."""
+
+    def __init__(self, device):
+        self._side = torch.cuda.Stream(device=device)
+        self._ready = [torch.cuda.Event(), torch.cuda.Event()]  # main -> side: slot free, RNG table consistent
+        self._done = [torch.cuda.Event(), torch.cuda.Event()]   # side -> main: slot filled
+        self.reset()
+
+    def reset(self):
+        """Nothing generated ahead, slot 0 next (a restored checkpoint: everything in flight has finished)."""
+        self.slot = 0          # the slot take() hands out: while `ahead`, the one generated ahead
+        self.ahead = False     # whether the next draw's randomness has been generated ahead
+        self._pending = None   # the event that marks it complete (None: nothing to wait for)
+
+    @property
+    def consumed(self):
+        """The slot the last take() handed out, once start_next() has moved on to the other one."""
+        return 1 - self.slot
+
+    def take(self, generate):
+        """-> the slot that holds this draw's randomness: generated ahead (the current stream waits for its generator), or
+        generated in line now (the first draw after a start, a drop or a reset)."""
+        if not self.ahead:
+            generate(self.slot)
+        elif self._pending is not None:
+            torch.cuda.current_stream().wait_event(self._pending)
+        return self.slot
+
+    def start_next(self, generate, keep=None):
+        """Queue the next draw's generator on the side stream, into the other slot, behind everything queued on the current
+        stream so far: that slot was last read by the previous draw's kernels, and the RNG table is shared, so the side
+        stream also starts after anything generated in line.  keep = (copy, table): the table as it is in front of the
+        generator -- the logical stream position while this slot is the one ahead -- is copied first."""
+        main, nxt = torch.cuda.current_stream(), 1 - self.slot
+        ready, done = self._ready[nxt], self._done[nxt]
+        ready.record(main)
+        self._side.wait_event(ready)
+        with torch.cuda.stream(self._side):
+            if keep is not None:
+                keep[0].copy_(keep[1])
+            generate(nxt)
+            done.record(self._side)
+        self._pending, self.slot, self.ahead = done, nxt, True
+
+    def drop(self, wait):
+        """Between two draws: what was generated ahead is not used (the next take() generates in line, into the same slot);
+        wait: the current stream first waits for its generator, which shares the RNG table with whatever comes next."""
+        if wait and self.ahead and self._pending is not None:
+            torch.cuda.current_stream().wait_event(self._pending)
+        self.ahead, self._pending = False, None
+
+    def already_joined(self):
+        """Between two draws, for a caller that keeps what is ahead: the draw that queued the generator has joined it, so
+        the next take() does not wait again.  Sound only right after join() on the same stream."""
+        self._pending = None
+
+    def join(self):
+        """Order everything queued later on the current stream after the pending generator
+        (its buffers were allocated on the main stream: without this a sampler dropped right after a draw
+        could see them handed to the next allocation while still being written).  A GPU-side wait: free
+        when the generator has finished, and the next draw's first kernel waits for the same event anyway."""
+        if self._pending is not None:
+            torch.cuda.current_stream().wait_event(self._pending)
+
+    def synchronize(self):
+        """The host waits for the pending generator (before it reads what the generator writes)."""
+        if self._pending is not None:
+            self._pending.synchronize()
+
+    def drain(self):
+        self._side.synchronize()
+
+
+# ---------------------------------------------------------------------------------------
 # engine base
 # ---------------------------------------------------------------------------------------
 PATHS = ("auto", "step", "opaque")
@@ -524,33 +611,17 @@ class ManyChainSampler:
     def __next__(self):
         return self.sample()
 
-    # -- the RNG side stream ----------------------------------------------------------------------------
-    # Events are created ONCE per sampler and re-recorded every draw.  Creating two torch.cuda.Event
-    # objects per draw and dropping them while GPU-side waits on them were still pending corrupted the
-    # host heap under the randomised soak (glibc "malloc(): invalid size", a chain off by one ulp) --
-    # about once per 100,000 short-lived samplers, more often the more events a draw used
-    # (tensor.record_stream() made it frequent).  With persistent events, a GPU-side join at the end of
-    # every draw and a drained side stream before the sampler's buffers are released, it is gone.
-    def _init_side_stream(self):
-        dev = self._ops.device
-        self._side = torch.cuda.Stream(device=dev)
-        self._ev_ready = [torch.cuda.Event(), torch.cuda.Event()]  # main -> side: slot free, RNG table consistent
-        self._ev_done = [torch.cuda.Event(), torch.cuda.Event()]   # side -> main: slot filled
+    _ahead = None  # the LookAhead of a sampler that generates the next draw's randomness ahead (prefetch_rng)
 
-    def _join_side_stream(self):
-        """Order everything queued later on the main stream after the side stream's pending generator
-        (its buffers were allocated on the main stream: without this a sampler dropped right after a draw
-        could see them handed to the next allocation while still being written).  A GPU-side wait: free
-        when the generator has finished, and the next draw's first kernel waits for the same event anyway."""
-        ev = getattr(self, "_pf_event", None)
-        if ev is not None and getattr(self, "_prefetch", False):
-            torch.cuda.current_stream().wait_event(ev)
+    def _join_ahead(self):
+        """At the end of a draw: see LookAhead.join."""
+        if self._ahead is not None:
+            self._ahead.join()
 
     def __del__(self):
         try:
-            side = getattr(self, "_side", None)
-            if side is not None:
-                side.synchronize()  # nothing of this sampler is in flight when its events and buffers go
+            if self._ahead is not None:
+                self._ahead.drain()  # nothing of this sampler is in flight when its events and buffers go
         except Exception:  # interpreter shutdown
             pass
 

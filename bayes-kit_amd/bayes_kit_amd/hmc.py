@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._engine import ManyChainSampler
+from ._engine import LookAhead, ManyChainSampler
 from .adapt import TrajectoryAdam, jitter_steps, shrink_estimate
 from .diagnostics import RunningCovariance, _gather_sum
 
@@ -109,9 +109,8 @@ class HMCDiag(ManyChainSampler):
         self._stepsize = stepsize
         self._steps = steps
         self._chees = None     # warmup(adapt_trajectory=True): the scratch of the trajectory statistic (bk_chees_*)
-        # prefetch_rng (decided below): whether the NEXT draw's randomness has been generated ahead, the event that marks it
-        # complete (None: already joined), per slot the stream table before that slot's normals were generated
-        self._prefetch, self._pf_ready, self._pf_event, self._snap = False, False, None, None
+        # prefetch_rng (decided below); per slot the stream table before that slot's normals were generated
+        self._prefetch, self._snap = False, None
         self._T, self._jitter_n, self._last_steps = None, 0, None
         self._max_steps = self._check_max_steps(max_steps)
         self._graph_explicit = graph is True
@@ -210,7 +209,6 @@ class HMCDiag(ManyChainSampler):
         if prefetch_rng is None:
             prefetch_rng = self._batched and self._ops.device.type == "cuda"
         self._prefetch = bool(prefetch_rng) and self._batched and not self._use_graph
-        self._pf_slot = 0           # double-buffer slot holding the NEXT draw's randomness
         self._pf_kin_stale = False
         if self._prefetch:
             if self._fused_zt:
@@ -220,7 +218,7 @@ class HMCDiag(ManyChainSampler):
                 self._rho_bufs.append(torch.empty((D, C), **f64))
             self._kin0_bufs.append(torch.empty(C, **f64))
             self._logu_bufs.append(torch.empty(C, **f64))
-            self._init_side_stream()
+            self._ahead = LookAhead(dev)
             if self._fused_zt:
                 self._snap = [torch.empty_like(self._rng_state) for _ in range(2)]
             else:
@@ -274,19 +272,18 @@ class HMCDiag(ManyChainSampler):
         """The tensor that holds the logical stream position (a sampler's without prefetch_rng): the table -- while the next
         draw's randomness is generated ahead, the table as it was when that generation began, which is snap[slot], written
         by the chain-major generator itself, or else _rng_logical, a copy queued in front of the generator."""
-        if self._prefetch and self._pf_ready:
-            return self._rng_logical if self._snap is None else self._snap[self._pf_slot]
+        if self._prefetch and self._ahead.ahead:
+            return self._rng_logical if self._snap is None else self._snap[self._ahead.slot]
         return self._rng_state
 
     def _drop_ahead(self, rewind):
         """Between two draws: drop the randomness generated ahead, once its generator has finished (a GPU-side wait);
         rewind: and take the stream back to where its generation began, for the next draw to generate it again."""
-        if self._prefetch and self._pf_ready:
-            if self._pf_event is not None:
-                torch.cuda.current_stream().wait_event(self._pf_event)
+        if self._prefetch and self._ahead.ahead:
+            position = self._stream_position()
+            self._ahead.drop(wait=True)
             if rewind:
-                self._rng_state.copy_(self._stream_position())
-            self._pf_ready, self._pf_event = False, None
+                self._rng_state.copy_(position)
 
     # -- the proper diagonal preconditioner -----------------------------------------------------------
     def _install_precond(self, v):
@@ -578,12 +575,12 @@ class HMCDiag(ManyChainSampler):
         return {"theta": self._theta_dc, "grad": self._grad, "lp": self._lp, "accepted": self._accepted}
 
     def _logical_rng(self):
-        if self._prefetch and self._pf_ready and self._pf_event is not None:
-            self._pf_event.synchronize()
+        if self._prefetch and self._ahead.ahead:
+            self._ahead.synchronize()
         return self._stream_position()
 
     def load_state_dict(self, sd):
-        if self._prefetch and self._pf_ready:
+        if self._prefetch and self._ahead.ahead:
             torch.cuda.synchronize()  # (the generator queued ahead has finished before its bookkeeping goes)
         self._drop_ahead(rewind=False)
         if self._rebind:
@@ -616,12 +613,8 @@ class HMCDiag(ManyChainSampler):
 
     def _after_load(self):
         # drop any randomness generated ahead: it is regenerated from the restored stream
-        self._pf_event, self._pf_slot, self._pf_ready, self._pf_kin_stale = None, 0, False, False
-
-    def _refresh_stale_kinetic(self):
-        if self._pf_kin_stale and self._pf_ready and not self._fused_draw:
-            self._ops.leapfrog_finish(self._rho_bufs[self._pf_slot], None, None, self._metric_dev, 0.0, False,
-                                      self._kin0_bufs[self._pf_slot])
+        if self._prefetch:
+            self._ahead.reset()
         self._pf_kin_stale = False
 
     def _randomness(self, slot):
@@ -666,8 +659,8 @@ class HMCDiag(ManyChainSampler):
         return self._gp_raw
 
     # The side-stream generator (prefetch_rng) runs ONE draw ahead: at the start of draw n the generator
-    # of draw n+1 is queued.  `_pf_slot` is the slot the next draw consumes; _stream_position() is where the
-    # reference's generator would be between two sample() calls.
+    # of draw n+1 is queued (_engine.LookAhead).  _stream_position() is where the reference's generator would be between
+    # two sample() calls.
     # For the one-pass draw (bk_hmc_draw), which is fp64-VALU bound like the generator, two other
     # schedules were measured at 65,536 x 1024 on one box (tools/fused_hmc_profile_run.py): queueing the
     # generator of draw n+2 right after draw n's accept test, so that it starts under the HBM-bound
@@ -675,37 +668,21 @@ class HMCDiag(ManyChainSampler):
     # (1.0-1.1 ms instead of 0.78) -- and no side stream at all, 1.38 ms; one ahead gives 1.29 ms: the
     # trajectories keep the ALUs, the generator takes what they leave and finishes under the blend.
     def _current_randomness(self):
-        """Buffers holding this draw's randomness (generated ahead with prefetch_rng)."""
-        self._zt_slot = 0 if not self._prefetch else self._pf_slot
+        """Buffers holding this draw's randomness; with prefetch_rng it was generated ahead, and the next draw's generator is
+        queued on the side stream, where it hides under this draw's launches."""
+        cur = 0
         if not self._prefetch:
             self._randomness(0)
-            return self._rho_bufs[0], self._kin0_bufs[0], self._logu_bufs[0]
-        cur = self._pf_slot
-        if not self._pf_ready:
-            self._randomness(cur)  # very first draw: nothing generated ahead yet
-            self._pf_kin_stale = False
         else:
-            if self._pf_event is not None:
-                torch.cuda.current_stream().wait_event(self._pf_event)
-            self._refresh_stale_kinetic()
+            ahead = self._ahead.ahead
+            cur = self._ahead.take(self._randomness)
+            if self._pf_kin_stale and ahead and not self._fused_draw:
+                # (the kinetic energy generated ahead was computed with a metric that has been replaced since)
+                self._ops.leapfrog_finish(self._rho_bufs[cur], None, None, self._metric_dev, 0.0, False, self._kin0_bufs[cur])
+            self._pf_kin_stale = False
+            self._ahead.start_next(self._randomness, None if self._snap is not None else (self._rng_logical, self._rng_state))
+        self._zt_slot = cur
         return self._rho_bufs[cur], self._kin0_bufs[cur], self._logu_bufs[cur]
-
-    def _start_next_randomness(self):
-        """Queue the next draw's generator on the side stream, into the other double-buffer slot (last
-        read by the previous draw's kernels, which are already queued on the main stream)."""
-        if not self._prefetch:
-            return
-        main = torch.cuda.current_stream()
-        nxt = 1 - self._pf_slot
-        ready, ev = self._ev_ready[nxt], self._ev_done[nxt]
-        ready.record(main)
-        self._side.wait_event(ready)
-        with torch.cuda.stream(self._side):
-            if self._snap is None:
-                self._rng_logical.copy_(self._rng_state)
-            self._randomness(nxt)
-            ev.record(self._side)
-        self._pf_event, self._pf_slot, self._pf_ready = ev, nxt, True
 
     def _graph_key(self):
         return (float(self._stepsize), int(self._steps))
@@ -817,7 +794,7 @@ class HMCDiag(ManyChainSampler):
         def draw():
             self._next_steps()
             self._draw()
-            self._join_side_stream()
+            self._join_ahead()
 
         metric = (self._dense_estimator if dense else self._diag_estimator) if adapt_metric else None
         try:
@@ -835,7 +812,7 @@ class HMCDiag(ManyChainSampler):
     def sample(self):
         self._next_steps()
         self._run_draw(self._draw)
-        self._join_side_stream()
+        self._join_ahead()
         self._draws += 1
         return self._draw_out(self._theta_dc, self._ret)
 
@@ -851,7 +828,6 @@ class HMCDiag(ManyChainSampler):
         # right after the D normals -- the same stream order as the reference, whose uniform is
         # the next value of the stream whatever happens in between
         rho, kin0, logu = self._current_randomness()
-        self._start_next_randomness()  # hides under this draw's launches
         # warmup(adapt_trajectory=True): the trajectory statistic reads the proposal's velocity, so the finish launch stores
         # it (in place) and the paths that keep it on chip or in a tile's scratch are not taken
         chees = self._chees is not None

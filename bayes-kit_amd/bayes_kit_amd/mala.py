@@ -35,7 +35,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._engine import ManyChainSampler
+from ._engine import LookAhead, ManyChainSampler
 
 
 class MALA(ManyChainSampler):
@@ -94,7 +94,6 @@ class MALA(ManyChainSampler):
         if prefetch_rng is None:
             prefetch_rng = self._batched and dev.type == "cuda"
         self._prefetch = bool(prefetch_rng) and self._batched and not self._use_graph
-        self._pf_slot, self._pf_ready, self._pf_event = 0, False, None
         # Philox streams: the normals come from the wavefront-per-chain generator, chain-major
         # (zt[c, d]); the consuming kernel turns them through LDS.  Otherwise (PCG64 host-seeded
         # single chains, tiny D): one lane per chain, normals in the state layout.
@@ -123,16 +122,14 @@ class MALA(ManyChainSampler):
         if self._prefetch or self._two_pass:
             self._logu_bufs = [torch.empty(C, **f64) for _ in range(nbuf)]
         if self._prefetch:
-            self._init_side_stream()
-            self._rng_logical = self._rng_state.clone()
+            self._ahead = LookAhead(dev)
+            self._rng_logical = self._rng_state.clone()  # step by step: the table in front of the generator queued ahead
         # two-pass pipeline: theta_p holds the proposal of the NEXT draw (made by the previous
         # draw's kernel from normals generated one draw ahead).  A generation unit is
         # (U_n, Z_{n+1}): the accept uniform of draw n, then the D normals of draw n+1 -- stream
         # order.  The LOGICAL stream position after draw n lies inside unit n (after U_n): it is
         # snapshotted there, per double-buffer slot.
         self._pipe_valid = False   # theta_p is the proposal of the next draw
-        self._unit_ready = False   # slot _pf_slot holds the next draw's unit (prefetch)
-        self._cur_slot = 0         # slot whose unit the last draw consumed
         if self._two_pass:
             self._snap = [torch.empty_like(self._rng_state) for _ in range(nbuf)]
         # ONE chain driven by a reference-style host model (the README example, config 1): after the model call a draw is
@@ -232,15 +229,21 @@ class MALA(ManyChainSampler):
 
     def _drop_ahead(self):
         """Step by step with prefetch_rng, between two draws: drop the randomness generated ahead and take the stream back to
-        where that began (the draw that queued the generator has joined it: _join_side_stream)."""
-        if self._prefetch and self._pf_ready:
+        where that began (the draw that queued the generator has joined it: LookAhead.join)."""
+        if self._prefetch and not self._two_pass and self._ahead.ahead:
             self._rng_state.copy_(self._rng_logical)
-        self._pf_ready, self._pf_event = False, None
+            self._ahead.drop(wait=False)
 
     def _invalidate_pipe(self, restore_stream):
+        """Between two draws (the last one has joined the generator queued ahead): the proposal made ahead is discarded,
+        and with it, two-pass, the unit generated ahead; step by step the randomness generated ahead stays valid."""
         if (self._two_pass or getattr(self, "_single", False)) and self._pipe_valid and restore_stream:
             self._rng_state.copy_(self._logical_rng())  # un-consume what was generated ahead
-        self._pipe_valid, self._unit_ready, self._pf_event = False, False, None
+        self._pipe_valid = False
+        if self._prefetch and self._two_pass:
+            self._ahead.drop(wait=False)
+        elif self._prefetch:
+            self._ahead.already_joined()
         self._drop_graphs()
 
     def _tune_placement(self):
@@ -280,10 +283,9 @@ class MALA(ManyChainSampler):
                 return self._rng_state
             if self._ops.device.type == "cuda":
                 torch.cuda.synchronize()
-            return self._snap[self._cur_slot]
-        if self._prefetch and self._pf_ready:
-            if self._pf_event is not None:
-                self._pf_event.synchronize()
+            return self._snap[self._ahead.consumed if self._prefetch else 0]  # (inside the unit the last draw consumed)
+        if self._prefetch and self._ahead.ahead:
+            self._ahead.synchronize()
             return self._rng_logical
         return self._rng_state
 
@@ -308,7 +310,8 @@ class MALA(ManyChainSampler):
 
     def _after_load(self):
         self._grad_stale = False  # (the gradient of the restored point came with it)
-        self._pf_event, self._pf_slot, self._pf_ready = None, 0, False
+        if self._prefetch:
+            self._ahead.reset()
         self._invalidate_pipe(restore_stream=False)  # the stream was just restored to its logical position
 
     def _gen(self, slot):
@@ -320,20 +323,8 @@ class MALA(ManyChainSampler):
         self._ops.log_uniform(self._rng_kind, self._rng_state, self._logu_bufs[slot])
 
     def _take_randomness(self):
-        main = torch.cuda.current_stream()
-        cur, nxt = self._pf_slot, 1 - self._pf_slot
-        if not self._pf_ready:
-            self._gen(cur)
-        elif self._pf_event is not None:
-            main.wait_event(self._pf_event)
-        ready, ev = self._ev_ready[nxt], self._ev_done[nxt]
-        ready.record(main)
-        self._side.wait_event(ready)
-        with torch.cuda.stream(self._side):
-            self._rng_logical.copy_(self._rng_state)
-            self._gen(nxt)
-            ev.record(self._side)
-        self._pf_event, self._pf_slot, self._pf_ready = ev, nxt, True
+        cur = self._ahead.take(self._gen)
+        self._ahead.start_next(self._gen, (self._rng_logical, self._rng_state))
         return self._z_bufs[cur], self._logu_bufs[cur]
 
     # -- two-pass: generation units (U_n, Z_{n+1}) ------------------------------------------------------
@@ -342,58 +333,25 @@ class MALA(ManyChainSampler):
         ops.log_uniform(self._rng_kind, self._rng_state, self._logu_bufs[slot])     # U_n   [metropolis.py:74]
         # Z_{n+1} [mala.py:44]; the generator leaves the table as it found it -- the position after draw n
         # -- in snap[slot]
-        ops.normals_chain_major(self._rng_kind, self._rng_state, self._zt_bufs[slot], self._dim, self._snap[slot],
-                                max_workgroups=self.generator_workgroups if self._prefetch else 0)
+        ops.normals_chain_major(self._rng_kind, self._rng_state, self._zt_bufs[slot], self._dim, self._snap[slot])
 
+    # The schedule is fixed: the generator of the next unit is queued on the side stream with the model's launch, on its
+    # own grid, and the step kernel does not wait for it.  Rounds 2-5 serialized the two -- the generator needed 169
+    # registers per lane, could not sit beside a step workgroup (192 x 512 threads per CU), and they only slowed each other
+    # down (1.52 against 1.3 ms per draw).  Round 6's generator needs 93 and finishes in 0.26-0.29 ms: letting its tail run
+    # under the step kernel is the fastest of the 32 schedules measured (65,536 x 1024, one box: model-opaque 1.124 ms
+    # against 1.152 serialized, density inlined 0.802 against 0.876; starting it with the step kernel instead, or on a
+    # grid bounded to one to four workgroups per CU, lost too: profiles/r6_mala.md).  Results never depended on it (events order the data).
     def _take_unit(self):
         """(log u of this draw, chain-major normals of the next); with prefetch also starts the
         unit after that on the side stream."""
+        cur = 0
         if not self._prefetch:
             self._gen_unit(0)
-            self._cur_slot = 0
-            return self._logu_bufs[0], self._zt_bufs[0]
-        main = torch.cuda.current_stream()
-        cur, nxt = self._pf_slot, 1 - self._pf_slot
-        if not self._unit_ready:
-            self._gen_unit(cur)  # first draw after a (re)start: nothing generated ahead yet
-        elif self._pf_event is not None:
-            main.wait_event(self._pf_event)
-        self._pf_slot, self._unit_ready, self._cur_slot = nxt, True, cur
-        if self.generate_with == "grad":
-            self._start_unit(nxt)
+        else:
+            cur = self._ahead.take(self._gen_unit)
+            self._ahead.start_next(self._gen_unit)
         return self._logu_bufs[cur], self._zt_bufs[cur]
-
-    def _start_unit(self, nxt, recorded=False):
-        """Queue the generator of the next unit on the side stream, behind everything queued on the main
-        stream so far (or up to where the caller recorded the slot's ready event).  Slot nxt was last read by
-        the previous draw's kernel, already queued on `main`; the RNG table is shared, so the side stream also
-        starts after anything generated in line."""
-        main = torch.cuda.current_stream()
-        ready, ev = self._ev_ready[nxt], self._ev_done[nxt]
-        if not recorded:
-            ready.record(main)
-        self._side.wait_event(ready)
-        with torch.cuda.stream(self._side):
-            self._gen_unit(nxt)
-            ev.record(self._side)
-        self._pf_event = ev
-
-    # Whether the step kernel waits for the generator of the next unit (queued on the side stream with the model's
-    # launch).  Rounds 2-5: yes -- the generator needed 169 registers per lane, could not sit beside a step workgroup
-    # (192 x 512 threads per CU), and the two only slowed each other down (1.52 against 1.3 ms per draw).  Round 6's
-    # generator needs 93 and finishes in 0.26-0.29 ms: letting its tail run under the step kernel is the fastest of the
-    # 32 schedules measured (65,536 x 1024, one box: model-opaque 1.124 ms against 1.152 serialized, density inlined
-    # 0.802 against 0.876; profiles/r6_mala.md).  Results do not depend on it (events order the data).
-    serialize_step = False
-    # When the generator of the next unit starts: "grad" = with the model's gradient op (then, with
-    # serialize_step, the step kernel waits for it), "step" = together with the step kernel, behind the
-    # gradient op (the step kernel's workgroups are queued first and take one slot per CU; a generator
-    # workgroup fits beside each: 160 of the 256 free registers per SIMD lane, 6 of the 27 free KB of LDS).
-    generate_with = "grad"
-    # Workgroups of the side-stream generator (0 = one per 16 chains, the kernel's own grid).  A bound of one per CU
-    # turns it into a background kernel with one wavefront per SIMD, beside which a step workgroup still fits.
-    generator_workgroups = 0
-    step_first = True  # (experiments: with generate_with = "step", which of the two is queued first)
 
     def accept_rate(self) -> float:
         n = self._draws * self._C
@@ -456,7 +414,7 @@ class MALA(ManyChainSampler):
         self._run_draw(self._draw2 if self._two_pass else self._draw)
         if self._sep_step:
             self._grad_stale = True  # (here, not in _draw2: a replayed hipGraph does not run the Python of the draw)
-        self._join_side_stream()
+        self._join_ahead()
         self._draws += 1
         if self._two_pass and not self._use_graph:
             return self._theta_dc.t(), self._ret.clone()  # the new state array itself (never written again)
@@ -472,7 +430,7 @@ class MALA(ManyChainSampler):
             # proposals are written by the previous draw's kernel
             ops.normals_chain_major(self._rng_kind, self._rng_state, self._zt_bufs[0], self._dim)
             self._propose(th, self._fresh_grad(), self._z_bufs[0], thp, eps)
-            self._pipe_valid, self._unit_ready, self._pipe_eps = True, False, eps
+            self._pipe_valid, self._pipe_eps = True, eps
         logu, zt_next = self._take_unit()
         if self._sep_step:
             self._eval_logp(thp, self._lp_p)                                                   # mala.py:46-48, log density
@@ -481,15 +439,6 @@ class MALA(ManyChainSampler):
         else:
             gp = self._materialize(self._eval_grad(thp, self._grad_p, self._lp_p), self._grad_p)   # mala.py:46-48
         out = th if self._use_graph else self._new_state()
-        with_step = self._prefetch and self.generate_with == "step"
-        if self._prefetch and self.serialize_step and self._pf_event is not None and not with_step:
-            torch.cuda.current_stream().wait_event(self._pf_event)
-        if with_step:
-            # both become runnable when the gradient op has finished; the step kernel's launch is handed to
-            # the hardware first
-            self._ev_ready[self._pf_slot].record(torch.cuda.current_stream())
-            if not self.step_first:
-                self._start_unit(self._pf_slot, recorded=True)
         if self._sep_step and self._pd is not None:
             self._model.bk_mala_step(th, out, thp, self._lp, self._lp_p, logu, zt_next, eps, s2,
                                      self._mask, self._ret, self._accepted, precond=self._pd)
@@ -502,8 +451,6 @@ class MALA(ManyChainSampler):
         else:
             ops.mala_step(th, out, self._grad, thp, gp, self._lp, self._lp_p, logu, zt_next, eps, s2,
                           self._mask, self._ret, self._accepted)                               # mala.py:50-66
-        if with_step and self.step_first:
-            self._start_unit(self._pf_slot, recorded=True)
         self._theta_dc = out
 
     def _draw(self):

@@ -1,14 +1,16 @@
-"""HMCDiag's randomness generated ahead (prefetch_rng) at the operations that have to drop it between two draws: a sampler
+"""HMCDiag's and MALA's randomness generated ahead (prefetch_rng) at the operations that have to drop it between two draws: a sampler
 that generates ahead and one that does not stay equal bit for bit -- stream position, draws, log densities -- across each
 of them.  130 chains (a ragged third wavefront, just past a 128-chain tile); D = 8 generates the momentum ahead in the state
 layout (the logical position is a copy queued in front of the generator), D = 40 chain-major normals (the generator's own
-snapshot)."""
+snapshot).  MALA: D = 8 runs step by step (the logical position is the copy in front of the generator), D = 40 two-pass (the
+snapshot inside the unit the last draw consumed)."""
 import numpy as np
 import pytest
 import torch
 
 import bayes_kit_amd as bk
 from tests import adapt_parity as ap
+from tests import mala_adapt_parity as mp
 from tests.test_gpu_providers import DIAG_SRC  # (the diagonal Gaussian as an elementwise bk_term)
 
 pytestmark = pytest.mark.gpu
@@ -67,7 +69,7 @@ def test_generating_ahead_changes_nothing_across(seam, D):
     assert a._fused_draw == b._fused_draw == fused_before
     assert (a._snap is not None) == (fused_before and D >= 32)
     _assert_equal_draws(a, b, 2, "before")
-    assert a._pf_ready  # (something was generated ahead for the operation to drop)
+    assert a._ahead.ahead  # (something was generated ahead for the operation to drop)
     op(a), op(b)
     assert a._fused_draw == b._fused_draw == fused_after
     assert np.array_equal(a.rng_state(), b.rng_state())
@@ -84,10 +86,33 @@ def test_set_metric_dense_drops_the_momentum_ahead_without_a_rewind(D):
     M = np.diag(ap.perturbed_variances(_lam(D))) + 0.01
     a.set_metric_dense(M), b.set_metric_dense(M)
     torch.cuda.synchronize()
-    assert not a._pf_ready
+    assert not a._ahead.ahead
     assert np.array_equal(a.rng_state(), a._rng_state.cpu().numpy().view(np.uint64))  # (the raw table: nothing rewound)
     assert not np.array_equal(a.rng_state(), b.rng_state())
     b.sample()
     assert np.array_equal(a.rng_state(), b.rng_state())
     ap.run_draws(a, 2), ap.run_draws(b, 2)
     assert np.array_equal(a.rng_state(), b.rng_state())
+
+
+# ---- MALA ------------------------------------------------------------------------------------------------------------------
+MALA_SEAMS = {
+    "refresh_cache()": lambda s: s.refresh_cache(),
+    "epsilon assigned": lambda s: setattr(s, "_epsilon", 0.8 * s._epsilon),
+    "set_precond_diag": _precond,
+    "load_state_dict(state_dict())": lambda s: s.load_state_dict(s.state_dict()),
+    "warmup(25)": lambda s: s.warmup(25),
+}
+
+
+@pytest.mark.parametrize("D", [8, 40])
+@pytest.mark.parametrize("seam", list(MALA_SEAMS))
+def test_mala_generating_ahead_changes_nothing_across(seam, D):
+    a, b = (mp.make(None, C, D, seed=19, prefetch_rng=pf, graph=False) for pf in (True, False))
+    assert a._prefetch and not b._prefetch
+    assert a._two_pass == b._two_pass == (D == 40)
+    _assert_equal_draws(a, b, 2, "before")
+    assert a._ahead.ahead  # (something was generated ahead for the operation to drop or keep)
+    MALA_SEAMS[seam](a), MALA_SEAMS[seam](b)
+    assert np.array_equal(a.rng_state(), b.rng_state())
+    _assert_equal_draws(a, b, 2, "after")
