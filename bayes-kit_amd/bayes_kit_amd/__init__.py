@@ -8,7 +8,7 @@ signatures, while the arithmetic runs in hand-written HIP kernels for gfx950
 """
 from . import _lib  # noqa: F401
 from . import dist  # noqa: F401
-from .diagnostics import DrawRecorder, DrawStore, RunningCovariance, RunningHistogram, RunningMoments, rhat_from_moments
+from .diagnostics import DrawRecorder, DrawStore, EnergyDiagnostics, RunningCovariance, RunningHistogram, RunningMoments, rhat_from_moments
 from .diagnostics import ess_bulk, ess_mean, ess_quantile, ess_tail, mcse_mean
 from .diagnostics import nested_rhat, nested_rhat_from_moments, superchain_init
 # like the reference (bayes_kit/__init__.py:2-13) the function names shadow the sub-modules of
@@ -60,6 +60,7 @@ __all__ = [
     "RunningMoments",
     "RunningCovariance",
     "RunningHistogram",
+    "EnergyDiagnostics",
     "DrawRecorder",
     "DrawStore",
     "rhat_from_moments",

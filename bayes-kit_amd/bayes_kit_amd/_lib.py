@@ -125,6 +125,9 @@ SIGNATURES = {
     "bk_accept_stat": [P, P, P, P, I, P, P, P],
     "bk_chees_sums": [P, I, P, I, P, I, I, P],
     "bk_chees_stat": [P, I, P, I, P, I, P, P, P, P, P, P, P, I, I, P],
+    "bk_energy_update": [P, P, P, P, P, F, P, P, P, P, P, P, P, P, P, P, I, P],
+    "bk_divergence_capture_work_elems": [I],
+    "bk_divergence_capture": [P, P, P, P, I, I, I, I, P, P, P, P, I, P, P, P],
     "bk_chain_mean_var": [P, I, P, I, P, P, I, P],
     "bk_end_pos_pairs": [P, I, I, P, I, P],
     "bk_ess": [P, I, I, c_int, P, P, I, P],
@@ -153,7 +156,7 @@ SIGNATURES = {
 }
 _RESTYPE = {"bk_gemm_chains_work_elems": c_int64, "bk_cov_k_chunk": c_int64, "bk_cov_accumulate_work_elems": c_int64, "bk_host_log1p": c_double, "bk_host_exp": c_double, "bk_refresh_work_elems": c_int64, "bk_sort_by_key_work_bytes": c_int64, "bk_resample_ordered_work_bytes": c_int64,
              "bk_autocorr_fft_work_bytes": c_int64, "bk_ess_multi_work_bytes": c_int64, "bk_ess_lag_sums_max_half": c_int64,
-             "bk_hist_lds_bins": c_int64, "bk_hist_slab_chains": c_int64}
+             "bk_hist_lds_bins": c_int64, "bk_hist_slab_chains": c_int64, "bk_divergence_capture_work_elems": c_int64}
 
 
 class BkHipError(RuntimeError):
@@ -439,6 +442,45 @@ class Ops:
             work = torch.empty(max(2, 2 * ((C + 255) // 256)), dtype=torch.float64, device=lp_cur.device)
         assert work.numel() >= 2 * ((C + 255) // 256)
         self._call("bk_accept_stat", ptr(lp_cur), ptr(a_cur), ptr(lp_prop), ptr(a_prop), C, ptr(out), ptr(work), self._s())
+
+    def energy_update(self, lp_cur, a_cur, lp_prop, a_prop, log_u, threshold, mean_E, m2_E, last_E, ssd, trans, cnt, ndiv,
+                      div_mask, err, totals):
+        """The energy error d = (lp_prop - a_prop) - (lp_cur - a_cur) of every chain, its divergence flag and the running
+        statistics of the selected energy (bk_energy_update), before mh_accept overwrites lp_cur.  Per-chain state: doubles
+        mean_E, m2_E, last_E, ssd, err and int64 trans, cnt, ndiv, uint8 div_mask, all [C] (contiguous slices of longer
+        vectors are fine); totals: int64 [4]."""
+        C = lp_cur.shape[0]
+        for t in (lp_prop, log_u, mean_E, m2_E, last_E, ssd, err):
+            assert t.dtype == torch.float64 and t.shape[0] == C and (C <= 1 or t.stride(0) == 1)
+        for t in (trans, cnt, ndiv):
+            assert t.dtype == torch.int64 and t.shape[0] == C and (C <= 1 or t.stride(0) == 1)
+        assert div_mask.dtype == torch.uint8 and div_mask.shape[0] == C and (C <= 1 or div_mask.stride(0) == 1)
+        assert totals.dtype == torch.int64 and totals.is_contiguous() and totals.numel() >= 4
+        self._call("bk_energy_update", ptr(lp_cur), ptr(a_cur), ptr(lp_prop), ptr(a_prop), ptr(log_u), float(threshold),
+                   ptr(mean_E), ptr(m2_E), ptr(last_E), ptr(ssd), ptr(trans), ptr(cnt), ptr(ndiv), ptr(div_mask), ptr(err),
+                   ptr(totals), C, self._s())
+
+    def divergence_capture_work_elems(self, C):
+        """int64 elements of scratch divergence_capture needs for C chains."""
+        return int(self.lib.bk_divergence_capture_work_elems(int(C)))
+
+    def divergence_capture(self, div_mask, err, trans, theta, chain0, theta_div, chain, draw, err_store, fill, work):
+        """Append the columns of theta [D, C] whose chains are flagged in div_mask to the store (theta_div [D, cap], chain,
+        draw, err_store [cap]; fill = {stored, seen}, int64 [2]) in ascending chain order; theta or theta_div None: the
+        flagged chains are counted in fill[1] only.  bk_divergence_capture."""
+        C = div_mask.shape[0]
+        assert fill.dtype == torch.int64 and fill.numel() >= 2 and work.dtype == torch.int64
+        assert work.numel() >= (C + 255) // 256 + 2
+        if theta is None or theta_div is None or theta_div.shape[1] == 0:
+            self._call("bk_divergence_capture", ptr(div_mask), 0, 0, 0, C, C, 0, int(chain0), 0, 0, 0, 0, 0, ptr(fill), ptr(work),
+                       self._s())
+            return
+        D, cap = theta_div.shape
+        assert tuple(theta.shape) == (D, C) and theta_div.is_contiguous() and theta.dtype == torch.float64
+        assert chain.numel() == cap and draw.numel() == cap and err_store.numel() == cap
+        assert chain.dtype == torch.int64 and draw.dtype == torch.int64 and trans.dtype == torch.int64
+        self._call("bk_divergence_capture", ptr(div_mask), ptr(err), ptr(trans), ptr(theta), _ld(theta), C, D, int(chain0),
+                   ptr(theta_div), ptr(chain), ptr(draw), ptr(err_store), cap, ptr(fill), ptr(work), self._s())
 
     def chees_sums(self, theta, theta_p, out):
         """out[d] = sum_c theta[d][c], out[D + d] = sum_c theta_p[d][c] (out may be longer than 2 D)."""

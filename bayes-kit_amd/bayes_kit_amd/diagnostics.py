@@ -576,6 +576,180 @@ class RunningHistogram:
         self.n = int(sd["n"])
 
 
+class EnergyDiagnostics:
+    """Divergent transitions and E-BFMI of an HMC run, tracked on the device: per-chain running statistics of the energy
+    error and of the selected energy, and a fixed store of the states divergent trajectories STARTED from.  No draw is kept
+    and nothing is read back per draw.
+
+    ``update`` takes the five vectors the HMC accept test reads (``bk_mh_accept(BK_ACCEPT_HMC)``: lp_cur, kin0, lp_prop,
+    kin1, log_u) BEFORE that test runs, and launches ``bk_energy_update`` -- the energy error ``d = (lp_prop - kin1) -
+    (lp_cur - kin0)`` in the accept test's own roundings, divergent where d is NaN or ``d < -threshold``, and the energy
+    ``E = -(selected joint log density)``, minus what ``sample()`` returns as logp -- then ``bk_divergence_capture``, which
+    appends the columns of ``theta`` of the divergent chains to the store: in call order, by ascending chain within a call,
+    the earliest ``capture`` entries kept and the rest counted (``seen``).  ``HMCDiag.track_energy()`` attaches one to a
+    sampler.
+
+    E-BFMI (Betancourt 2016) per chain is ``mean(diff(E)**2) / var(E)`` (ArviZ's estimator) over the chain's finite
+    energies; ``ebfmi_pooled`` pools the chains, for runs of many short chains.  A non-finite energy is counted
+    (``nonfinite_energies``) and skipped: the successive difference then spans the gap."""
+
+    _VECTORS = ("mean_E", "m2_E", "last_E", "ssd", "trans", "cnt", "ndiv", "div_mask", "err")
+    _STORE = ("theta_div", "chain", "draw", "err_store")
+
+    def __init__(self, C: int, D=None, threshold: float = 1000.0, capture: int = 1024, chain_id0: int = 0, ops=None):
+        self._ops = _ops(ops)
+        dev = self._ops.device
+        C, capture = int(C), int(capture)
+        threshold = float(threshold)
+        if C < 1:
+            raise ValueError(f"EnergyDiagnostics requires C >= 1 chains, but C = {C}")
+        if D is not None and int(D) < 1:
+            raise ValueError(f"EnergyDiagnostics requires D >= 1 (or None: no states are captured), but D = {D}")
+        if not (np.isfinite(threshold) and threshold > 0.0):
+            raise ValueError(f"EnergyDiagnostics requires a finite threshold > 0, but threshold = {threshold}")
+        if capture < 0:
+            raise ValueError(f"EnergyDiagnostics requires capture >= 0, but capture = {capture}")
+        self.C, self.D, self.threshold, self.chain_id0 = C, None if D is None else int(D), threshold, int(chain_id0)
+        self.capture = capture if D is not None else 0
+        f64, i64 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int64, device=dev)
+        self.mean_E, self.m2_E, self.last_E, self.ssd, self.err = (torch.zeros(C, **f64) for _ in range(5))
+        self.trans, self.cnt, self.ndiv = (torch.zeros(C, **i64) for _ in range(3))
+        self.div_mask = torch.zeros(C, dtype=torch.uint8, device=dev)
+        self._totals = torch.zeros(4, **i64)  # {transitions, divergent, NaN energy errors, non-finite energies}
+        self._fill = torch.zeros(2, **i64)    # {stored, seen}
+        cap = self.capture
+        self.theta_div = torch.zeros((self.D, cap), **f64) if cap else None
+        self.chain, self.draw = torch.zeros(cap, **i64), torch.zeros(cap, **i64)
+        self.err_store = torch.zeros(cap, **f64)
+        self._work = torch.zeros(self._ops.divergence_capture_work_elems(C), **i64)
+
+    def update(self, lp_cur, kin0, lp_prop, kin1, log_u, theta=None, chain0=None) -> None:
+        """One transition of every chain -- or, with ``chain0``, of the n = len(lp_cur) chains whose ids start at chain0
+        (a column slice: the tile-major schedule).  theta: the [D, n] state the trajectories start from (None: divergences
+        are counted, no state is captured).  Two entry points, three launches; no host read."""
+        n = lp_cur.shape[0]
+        c0 = 0 if chain0 is None else int(chain0) - self.chain_id0
+        if c0 < 0 or c0 + n > self.C or (chain0 is None and n != self.C):
+            raise ValueError(f"update: {n} chains from chain {self.chain_id0 + c0} do not lie inside this tracker's "
+                             f"{self.C} chains from {self.chain_id0}")
+        if theta is not None and self.theta_div is not None and tuple(theta.shape) != (self.D, n):
+            raise ValueError(f"update: theta must be the [D, n] = ({self.D}, {n}) start state, got {tuple(theta.shape)}")
+        sl = slice(c0, c0 + n)
+        ops = self._ops
+        ops.energy_update(lp_cur, kin0, lp_prop, kin1, log_u, self.threshold, self.mean_E[sl], self.m2_E[sl],
+                          self.last_E[sl], self.ssd[sl], self.trans[sl], self.cnt[sl], self.ndiv[sl], self.div_mask[sl],
+                          self.err[sl], self._totals)
+        ops.divergence_capture(self.div_mask[sl], self.err[sl], self.trans[sl], theta, self.chain_id0 + c0, self.theta_div,
+                               self.chain, self.draw, self.err_store, self._fill, self._work)
+
+    # -- read-outs (none runs per draw) --------------------------------------------------------------------------------
+    def _tot(self, group):
+        return _gather_sum(self._totals, group).cpu()
+
+    @property
+    def transitions(self) -> int:
+        """Transitions seen so far, over this rank's chains."""
+        return int(self._totals[0].item())
+
+    def divergences(self, group=None) -> int:
+        return int(self._tot(group)[1])
+
+    def divergence_rate(self, group=None) -> float:
+        t = self._tot(group)
+        return float(t[1]) / float(t[0]) if int(t[0]) else float("nan")
+
+    def nan_transitions(self, group=None) -> int:
+        """Transitions whose energy error was NaN (all of them are counted divergent)."""
+        return int(self._tot(group)[2])
+
+    def nonfinite_energies(self, group=None) -> int:
+        """Transitions whose selected energy was not finite (left out of the energy statistics)."""
+        return int(self._tot(group)[3])
+
+    @property
+    def divergences_per_chain(self) -> torch.Tensor:
+        return self.ndiv.clone()
+
+    @property
+    def last_divergent(self) -> torch.Tensor:
+        return self.div_mask.bool()
+
+    @property
+    def last_energy_error(self) -> torch.Tensor:
+        return self.err.clone()
+
+    def energy_mean(self) -> torch.Tensor:
+        """[C]: the mean of each chain's finite energies (NaN where it has none)."""
+        return torch.where(self.cnt > 0, self.mean_E, torch.full_like(self.mean_E, float("nan")))
+
+    def energy_var(self) -> torch.Tensor:
+        """[C]: their variance, ddof = 0 as in ``np.var`` (NaN where the chain has none)."""
+        n = self.cnt.to(torch.float64)
+        return torch.where(self.cnt > 0, self.m2_E / n.clamp(min=1.0), torch.full_like(self.m2_E, float("nan")))
+
+    def ebfmi(self) -> torch.Tensor:
+        """[C]: (ssd / (cnt - 1)) / (m2 / cnt) = mean(diff(E)**2) / var(E); NaN where cnt < 2 or m2 == 0."""
+        n = self.cnt.to(torch.float64)
+        ok = (self.cnt >= 2) & (self.m2_E != 0.0)
+        num = self.ssd / (n - 1.0).clamp(min=1.0)
+        den = torch.where(ok, self.m2_E / n.clamp(min=1.0), torch.ones_like(n))
+        return torch.where(ok, num / den, torch.full_like(num, float("nan")))
+
+    def ebfmi_pooled(self, group=None) -> float:
+        """sum_c ssd / sum_c (cnt - 1) over the variance of ALL energies pooled, (sum_c m2 + sum_c cnt (mean_c - grand)^2) /
+        sum_c cnt, over the chains of all ranks of ``group`` (two gathers: the sums, then the spread around the grand
+        mean).  NaN with fewer than one successive difference or a pooled variance of zero."""
+        n = self.cnt.to(torch.float64)
+        pairs = (self.cnt - 1).clamp(min=0).to(torch.float64)
+        mean = torch.where(self.cnt > 0, self.mean_E, torch.zeros_like(self.mean_E))
+        s = _gather_sum(torch.stack([self.ssd.sum(), pairs.sum(), self.m2_E.sum(), n.sum(), (n * mean).sum()]), group)
+        if float(s[1]) <= 0.0 or float(s[3]) <= 0.0:
+            return float("nan")
+        grand = s[4] / s[3]
+        dev = mean - grand
+        between = _gather_sum((n * dev * dev).sum().reshape(1), group)
+        var = (float(s[2]) + float(between[0])) / float(s[3])
+        return (float(s[0]) / float(s[1])) / var if var > 0.0 else float("nan")
+
+    def divergent_states(self) -> dict:
+        """The captured entries, oldest first: ``theta`` [n, D] (the states divergent trajectories started from), ``chain``
+        (global chain ids), ``draw`` (the chain's transition number, 1-based), ``energy_error``; ``stored`` = n and ``seen``,
+        the divergent transitions met (those past the capacity are counted only).  This rank's chains."""
+        stored, seen = (int(v) for v in self._fill.cpu())
+        th = None if self.theta_div is None else self.theta_div[:, :stored].t().contiguous()
+        return {"theta": th, "chain": self.chain[:stored].clone(), "draw": self.draw[:stored].clone(),
+                "energy_error": self.err_store[:stored].clone(), "stored": stored, "seen": seen}
+
+    def _tensors(self):
+        names = self._VECTORS + ("_totals", "_fill") + (self._STORE if self.theta_div is not None else self._STORE[1:])
+        return {k.lstrip("_"): getattr(self, k) for k in names}
+
+    def reset(self) -> None:
+        """Forget every transition and empty the store; threshold and capacity stay."""
+        for t in self._tensors().values():
+            t.zero_()
+
+    # checkpoint / resume: every tensor above; restored, the updates continue bit for bit
+    def state_dict(self):
+        sd = {k: t.detach().cpu().clone() for k, t in self._tensors().items()}
+        sd["meta"] = {"C": self.C, "D": self.D, "threshold": self.threshold, "capture": self.capture,
+                      "chain_id0": self.chain_id0}
+        return sd
+
+    def load_state_dict(self, sd):
+        meta = sd["meta"]
+        mine = {"C": self.C, "D": self.D, "threshold": self.threshold, "capture": self.capture, "chain_id0": self.chain_id0}
+        for k, v in mine.items():
+            if meta.get(k) != v:
+                raise ValueError(f"checkpoint holds an energy tracker with {k} = {meta.get(k)!r}, this one has {k} = {v!r}")
+        mine_t = self._tensors()
+        for k, t in mine_t.items():
+            if k not in sd or tuple(sd[k].shape) != tuple(t.shape) or sd[k].dtype != t.dtype:
+                raise ValueError(f"checkpoint holds no {k!r} of shape {tuple(t.shape)} and dtype {t.dtype}")
+        for k, t in mine_t.items():
+            t.copy_(sd[k].to(t.device))
+
+
 class DrawRecorder:
     """Draw storage for post-processing: the full series of a few tracked
     coordinates (and the returned log density) as ``[K, N, C]`` -- draw-major, chain-contiguous,

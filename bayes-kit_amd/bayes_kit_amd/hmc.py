@@ -27,7 +27,7 @@ import torch
 from . import _lib
 from ._engine import LookAhead, ManyChainSampler
 from .adapt import TrajectoryAdam, jitter_steps, shrink_estimate
-from .diagnostics import RunningCovariance, _gather_sum
+from .diagnostics import EnergyDiagnostics, RunningCovariance, _gather_sum
 
 
 class TrajectoryObserver:
@@ -498,6 +498,9 @@ class HMCDiag(ManyChainSampler):
                 ops.leapfrog_finish_precond(rho_k, None, gl, self._pd, half, False, self._kin1[sl])
             else:
                 ops.leapfrog_finish(rho_k, None, gl, m, half, False, self._kin1[sl])
+            if self._energy is not None:  # (this tile's log density and state columns are still the start's: no clone)
+                self._energy.update(self._lp[sl], kin0[sl], self._lp_p[sl], self._kin1[sl], logu[sl], th[:, sl],
+                                    chain0=self._chain_id0 + c0)
             ops.mh_accept(_lib.ACCEPT_HMC, self._lp[sl], kin0[sl], self._lp_p[sl], self._kin1[sl], logu[sl],
                           self._mask[sl], self._ret[sl], self._accepted)
             if self._rebind:
@@ -564,6 +567,35 @@ class HMCDiag(ManyChainSampler):
     @property
     def last_accept(self):
         return self._mask.bool() if self._batched else bool(self._mask[0].item())
+
+    # -- energy diagnostics ------------------------------------------------------------------------
+    _energy = None  # track_energy(): the diagnostics.EnergyDiagnostics fed before every accept test
+
+    def track_energy(self, threshold: float = 1000.0, capture: int = 1024) -> EnergyDiagnostics:
+        """Track divergent transitions (energy error NaN or below -threshold) and the energy statistics of E-BFMI from the
+        next draw on, and keep the states up to ``capture`` divergent trajectories started from; -> the tracker
+        (diagnostics.EnergyDiagnostics, also ``self.energy``), which owns all of its state in device memory and
+        checkpoints itself (``state_dict()`` of the sampler does not carry it).
+
+        Tracking changes no bit of theta, logp, the accept counter or the streams on any path.  The tracker's two entry
+        points run right before the accept test, on the five vectors that test reads and on the start state: three small
+        launches per draw (per tile on the tile-major schedule), no host read, nothing allocated -- a captured draw
+        (graph=True) replays them; graphs are captured again after this call.  Cost: the whole-draw kernel leaves its
+        accept test to a launch of its own while a tracker is attached (as during warmup()): one more launch.
+        warmup() works with a tracker attached and reports what it reports without one."""
+        self._energy = EnergyDiagnostics(self._C, self._dim, threshold, capture, self._chain_id0, self._ops)
+        self._drop_graphs()
+        return self._energy
+
+    def untrack_energy(self) -> None:
+        """Detach the tracker (it keeps its state): the draws go back to the launches of an untracked sampler."""
+        self._energy = None
+        self._drop_graphs()
+
+    @property
+    def energy(self):
+        """The attached EnergyDiagnostics (None: not tracking)."""
+        return self._energy
 
     def _set_metric(self, m):
         if self._pd is not None:
@@ -841,14 +873,14 @@ class HMCDiag(ManyChainSampler):
             # (fp64-VALU bound: a metric of ones is not multiplied in -- x * 1.0 is x, bit for bit)
             m_draw = None if (m is None or self._metric_identity) else m
             accept = (self._lp, logu, self._mask, self._ret, self._accepted)
-            in_launch = accept if self._stat is None else None
+            in_launch = accept if (self._stat is None and self._energy is None) else None
             if self._pd is not None:
                 self._model.bk_hmc_draw_precond(th, thp, rho, zt, self._pd, eps, L, self._part, kin0, self._kin1, self._lp_p,
                                                 accept=in_launch)
             else:
                 self._model.bk_hmc_draw(th, thp, rho, zt, m_draw, eps, L, self._part, kin0, self._kin1, self._lp_p,
                                         accept=in_launch)  # [hmc.py:56-63]
-            if in_launch is None:  # warmup: the statistic first, then the same accept arithmetic as its own launch
+            if in_launch is None:  # warmup / track_energy: their passes first, then the same accept arithmetic as its own launch
                 self._accept(kin0, logu)
             self._take(th, thp)
             return
@@ -940,9 +972,12 @@ class HMCDiag(ManyChainSampler):
 
     def _accept(self, kin0, logu):
         """The accept test [hmc.py:60-63]; during warmup() preceded by the acceptance statistic of the same energies
-        (bk_accept_stat, before the test overwrites the current log density)."""
+        (bk_accept_stat, before the test overwrites the current log density), and with track_energy() by the energy
+        diagnostics of the same five vectors and the capture of the divergent chains' start state."""
         if self._stat is not None:
             self._ops.accept_stat(self._lp, kin0, self._lp_p, self._kin1, self._stat, self._stat_work)
+        if self._energy is not None:
+            self._energy.update(self._lp, kin0, self._lp_p, self._kin1, logu, self._theta_dc)
         if self._chees is not None:
             self._chees_launch(kin0)
         self._ops.mh_accept(_lib.ACCEPT_HMC, self._lp, kin0, self._lp_p, self._kin1, logu,

@@ -1084,6 +1084,45 @@ int bk_chees_stat(const double* theta, int64_t ld, const double* theta_p, int64_
                   const double* mean, const double* lp_cur, const double* a_cur, const double* lp_prop,
                   const double* a_prop, double* out, double* work, int64_t C, int64_t D, void* stream);
 
+/* Energy diagnostics of an HMC accept test (EnergyDiagnostics): divergent transitions and the per-chain statistics of
+ * E-BFMI, from the five vectors bk_mh_accept(BK_ACCEPT_HMC, ...) is about to read -- call it BEFORE that test overwrites
+ * lp_cur.  One elementwise pass; per chain c, every operation rounded on its own, in this order:
+ *     h0 = lp_cur - a_cur;  h1 = lp_prop - a_prop;  d = h1 - h0;  acc = log_u < d        (bk_mh_accept's, bit for bit)
+ *     err[c] = d;   divergent = isnan(d) || d < -threshold;   div_mask[c] = divergent    (strict: d == -threshold is not;
+ *                                                                                         d = -inf is, d = +inf is not)
+ *     trans[c] += 1;   ndiv[c] += divergent
+ *     E = -(acc ? h1 : h0)                                   minus the value bk_mh_accept writes to `ret`
+ *     E not finite: counted in totals[3], the energy state stays as it is.  Otherwise
+ *         cnt[c] += 1;  delta = E - mean;  mean = mean + delta / cnt;  m2 = m2 + delta * (E - mean)       (Welford)
+ *         if this is not the chain's first finite energy:  t = E - last;  ssd = ssd + t * t
+ *         last = E
+ * totals[4] += {chains, divergent chains, chains whose d is NaN, chains whose E is not finite} of this call (64-bit integer
+ * atomics after a wavefront ballot; there are no floating-point atomics).  a_cur / a_prop NULL = zeros.  The doubles need
+ * 8-byte alignment only and the mask none: every array may be a column slice [c0, c1) of a larger one.
+ * BK_E_ARG, decided before any HIP call: a NULL pointer other than a_cur / a_prop, C < 0, a threshold that is not finite
+ * and > 0.  C == 0: BK_OK, nothing launched. */
+int bk_energy_update(const double* lp_cur, const double* a_cur, const double* lp_prop, const double* a_prop,
+                     const double* log_u, double threshold, double* mean_E, double* m2_E, double* last_E, double* ssd,
+                     int64_t* trans, int64_t* cnt, int64_t* ndiv, uint8_t* div_mask, double* err, int64_t* totals,
+                     int64_t C, void* stream);
+
+/* Keep the columns of the chains flagged in div_mask (bk_energy_update's) in a fixed store of `cap` entries:
+ *     theta_div[d][p] = theta[d][c] (theta [D][ld], theta_div [D][cap]),  chain[p] = chain0 + c,  draw[p] = trans[c],
+ *     err_store[p] = err[c],   fill = {entries stored, flagged chains seen}.
+ * The ORDER is a contract: entries fill in call order and, within a call, by ascending chain, whatever the launch geometry
+ * -- an exclusive scan of the flags per block of 256 chains (one workgroup, into `work`), then a gather over (block of
+ * chains, block of rows) in which a chain's position is the fill level the call found + its block's prefix + its rank in
+ * the block, re-derived from ballots.  No atomic takes part.  Flagged chains past `cap` are counted in fill[1] and not
+ * stored: the earliest are kept.  Both kernels are launched whatever the flags say (no host read); without a flag the
+ * gather's workgroups return at once.  cap == 0, a NULL theta_div or D == 0: fill[1] alone is counted.
+ * work: caller scratch of bk_divergence_capture_work_elems(C) = ceil(C / 256) + 2 int64.
+ * BK_E_ARG, decided before any HIP call: div_mask, fill or work NULL, C < 0, D < 0, cap < 0, D > 1,048,560; with a store:
+ * any other pointer NULL or ld < C.  C == 0: BK_OK, nothing launched. */
+int64_t bk_divergence_capture_work_elems(int64_t C);
+int bk_divergence_capture(const uint8_t* div_mask, const double* err, const int64_t* trans, const double* theta,
+                          int64_t ld, int64_t C, int64_t D, int64_t chain0, double* theta_div, int64_t* chain,
+                          int64_t* draw, double* err_store, int64_t cap, int64_t* fill, int64_t* work, void* stream);
+
 /* Per-chain mean and ddof=1 variance of a stored series x[t*ld + c], t < len[c] (len NULL =
  * all N): the two list comprehensions of rhat.py:165-166 for ragged chains. */
 int bk_chain_mean_var(const double* x, int64_t ld, const int32_t* len, int64_t N,
