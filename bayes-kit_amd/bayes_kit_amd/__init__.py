@@ -27,7 +27,7 @@ from .hmc import HMCDiag
 from .mala import MALA
 from .metropolis import ChainRng, Metropolis, MetropolisHastings
 from .smc import TemperedLikelihoodSMC, TorchPriorLikelihoodModel, hmc_kernel, mala_kernel, metropolis_kernel
-from .targets import CTarget, DiagGaussian, Funnel, IsoGaussian, LogisticRegression, TorchModel
+from .targets import GLM, CTarget, DiagGaussian, Funnel, IsoGaussian, LogisticRegression, TorchModel
 
 __all__ = [
     "DrGhmcDiag",
@@ -71,6 +71,7 @@ __all__ = [
     "DiagGaussian",
     "Funnel",
     "LogisticRegression",
+    "GLM",
     "TorchModel",
     "CTarget",
     "ChainRng",

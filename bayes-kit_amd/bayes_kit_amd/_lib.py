@@ -23,6 +23,7 @@ ACCEPT_HMC = 0
 ACCEPT_MALA = 1
 BK_RESAMPLE_SYSTEMATIC = 0
 BK_RESAMPLE_STRATIFIED = 1
+GLM_FAMILIES = ("bernoulli", "binomial", "poisson", "gaussian")  # BK_GLM_* of include/bkhip.h, by index
 
 P = c_void_p
 I = c_int64
@@ -133,6 +134,8 @@ SIGNATURES = {
     "bk_ess": [P, I, I, c_int, P, P, I, P],
     "bk_iat_from_acor": [P, I, I, c_int, P, P, I, P],
     "bk_gemm_chains_logistic": [P, I, I, I, P, I, P, I, I, P, P],
+    "bk_gemm_chains_glm": [P, I, I, I, P, I, P, I, I, c_int, P, P, P, P],
+    "bk_glm_residual": [P, I, c_int, P, P, P, P, I, I, I, P],
     "bk_autocorr": [P, I, I, P, I, I, P],
     "bk_autocorr_fft_work_bytes": [I, I],
     "bk_autocorr_fft": [P, I, I, P, I, I, P, I, P],
@@ -1049,6 +1052,23 @@ class Ops:
         launch is cut into (its parallelism over the observations)."""
         N, C = Z.shape
         self._call("bk_logistic_residual", ptr(Z), _ld(Z), ptr(y), ptr(part), N, C,
+                   part.shape[0] if part is not None else int(segments or 256), self._s())
+
+    def gemm_chains_glm(self, A, X, Y, family, y_rows, aux_rows=None, offset_rows=None):
+        """Y[R, C] = the GLM residual (include/bkhip.h, "GLM targets") of A[R, K] @ X[K, C] with the rows' y, aux (trials /
+        precision) and offset: gemm_chains + glm_residual(part=None) in one launch.  family: a GLM_FAMILIES index."""
+        R, K = A.shape
+        assert X.shape[0] == K and Y.shape[0] == R and y_rows.numel() == R
+        assert all(v is None or (v.numel() == R and v.is_contiguous()) for v in (aux_rows, offset_rows))
+        self._call("bk_gemm_chains_glm", ptr(A), _ld(A), R, K, ptr(X), _ld(X), ptr(Y), _ld(Y), X.shape[1], int(family),
+                   ptr(y_rows), ptr(aux_rows), ptr(offset_rows), self._s())
+
+    def glm_residual(self, Z, family, y, aux, offset, part, segments=None):
+        """Z <- the GLM residual in place, part[s] <- the s-th row block's log-likelihood terms summed in row order.  part
+        None: gradient only; `segments` then still says how many row blocks the launch is cut into."""
+        N, C = Z.shape
+        assert y.numel() == N and all(v is None or (v.numel() == N and v.is_contiguous()) for v in (aux, offset))
+        self._call("bk_glm_residual", ptr(Z), _ld(Z), int(family), ptr(y), ptr(aux), ptr(offset), ptr(part), N, C,
                    part.shape[0] if part is not None else int(segments or 256), self._s())
 
     def logistic_finish(self, G, theta, part, inv_prior_var, t, grad, logp, loglik):

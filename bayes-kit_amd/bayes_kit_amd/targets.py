@@ -197,24 +197,35 @@ class Funnel(_BuiltinTarget):
         return True
 
 
-class LogisticRegression(_BuiltinTarget):
-    """Bayesian logistic regression, y_n ~ Bernoulli(sigmoid(x_n . theta)), theta ~ N(0, s^2 I)
-    (BASELINE.json config 5; no reference counterpart).  The gradient for ALL chains is two
-    fp64 MFMA GEMMs -- Z = X @ Theta (N x C) and G = X^T @ (y - sigmoid(Z)) (D x C) -- with one
-    elementwise pass in between; also a batched LogPriorLikelihoodModel (typing.py:37-42) with
-    a likelihood temperature for smc.py's annealing."""
+class _LinearPredictorTarget(_BuiltinTarget):
+    """What the regression targets with one linear predictor share: theta ~ N(0, s^2 I), a likelihood whose gradient for
+    ALL chains is two fp64 MFMA GEMMs -- Z = X @ Theta (N x C) and G = X^T @ r(Z) (D x C) -- with one cell-wise map in
+    between, the buffers, the finish (grad = t G - theta / s^2, logp = t loglik + log prior) and the tempering split.  A
+    subclass says how the residual is formed: ``_residual_epilogue`` (gradient only, in the first GEMM's epilogue) and
+    ``_residual_pass`` (the stand-alone pass that also forms the log-likelihood partial sums); ``_ll_const`` is the sum
+    of the observations' normalising constants (0.0: nothing is added)."""
 
-    _kind = "logistic"
     bk_counted = False  # (two GEMMs over all chains: no counted form)
     SEGMENTS = 256  # blocks of observations whose log-likelihood partial sums are combined in order
+    _ll_const = 0.0
 
-    def __init__(self, X, y, prior_scale: float = 1.0, ops=None):
+    def __init__(self, X, prior_scale, ops):
         X = torch.as_tensor(X, dtype=torch.float64)
         super().__init__(X.shape[1], ops)
         self._N = int(X.shape[0])
-        self._X_host, self._y_host = X, torch.as_tensor(y, dtype=torch.float64).reshape(-1)
+        self._X_host = X
         self._inv_s2 = 1.0 / float(prior_scale) ** 2
         self._dev = None
+
+    def _row_data(self, device):
+        """{name: [N] device tensor} of the per-observation arrays the residual hooks read."""
+        raise NotImplementedError
+
+    def _residual_epilogue(self, ops, b, theta_dc, Z):
+        raise NotImplementedError
+
+    def _residual_pass(self, ops, b, Z, part, segments):
+        raise NotImplementedError
 
     def _buffers(self, device, C, ld):
         """Scratch for C chains whose state rows are `ld` apart (G shares the state's pitch: the finish kernel walks
@@ -222,14 +233,25 @@ class LogisticRegression(_BuiltinTarget):
         ops = self._get_ops()
         if self._dev is None or self._dev["X"].device != device:
             X = self._X_host.to(device).contiguous()
-            self._dev = {"X": X, "Xt": X.t().contiguous(), "y": self._y_host.to(device).contiguous(), "C": 0, "ld": 0}
+            self._dev = {"X": X, "Xt": X.t().contiguous(), "C": 0, "ld": 0, "parts": {}}
+            self._dev.update(self._row_data(device))
         b = self._dev
         f64 = dict(dtype=torch.float64, device=device)
         if b["C"] < C:
             b["Z"] = torch.empty((self._N, C), **f64)
-            b["part"] = torch.empty((min(self.SEGMENTS, max(1, self._N)), C), **f64)
             b["work"] = ops.gemm_chains_work(self._D, self._N, C)  # split-K slabs of X^T r (a function of D, N only)
             b["C"] = C
+        if C not in b["parts"]:
+            # part[s * C + c]: the kernels' pitch is the call's C, so every width has a [S (+ 1), C] array OF ITS OWN, kept
+            # for the model's life.  Where the likelihood has a normalising constant its last row holds it (the finish
+            # sums it in after the segments), written here once.  That row is the one datum in these buffers that is not
+            # scratch: no evaluation at another width, and no growth of Z, may touch it -- a captured draw replays
+            # without this code and reads the row as it was left.
+            S = min(self.SEGMENTS, max(1, self._N))
+            rows = torch.empty((S + (1 if self._ll_const != 0.0 else 0), C), **f64)
+            if rows.shape[0] > S:
+                rows[S].fill_(self._ll_const)
+            b["S"], b["parts"][C] = S, rows
         if b["ld"] != ld:
             b["G"] = torch.empty((self._D, ld), **f64)
             b["ld"] = ld
@@ -237,27 +259,27 @@ class LogisticRegression(_BuiltinTarget):
 
     def bk_eval(self, theta_dc, grad_out, logp_out, t: float = 1.0, loglik_out=None, gll_out=None):
         """t: likelihood temperature (log density = t * loglik + logprior).  loglik_out ([C]) / gll_out ([D, C], the
-        state's pitch): the UNTEMPERED log likelihood and its gradient X^T (y - sigmoid(X theta)) of the evaluated
+        state's pitch): the UNTEMPERED log likelihood and its gradient X^T r(X theta) of the evaluated
         points -- what bk_retemper() turns into (logp, grad) at another temperature without touching the data."""
         ops = self._get_ops()
         D, C = theta_dc.shape
         b = self._buffers(theta_dc.device, C, _lib._ld(theta_dc))
         Z = b["Z"][:, :C]
         # (a leapfrog step wants the gradient alone: the residual pass then skips the log likelihood)
-        part = b["part"][:, :C] if (logp_out is not None or loglik_out is not None) else None
+        part = b["parts"][C] if (logp_out is not None or loglik_out is not None) else None
         if part is None:
-            ops.gemm_chains_logistic(b["X"], theta_dc, Z, b["y"])        # r = y - sigmoid(X theta): residual in the epilogue
+            self._residual_epilogue(ops, b, theta_dc, Z)                 # r(X theta): residual in the epilogue
         else:
             ops.gemm_chains(b["X"], theta_dc, Z)                          # z = X theta          (MFMA)
-            ops.logistic_residual(Z, b["y"], part, b["part"].shape[0])  # r = y - sigmoid(z), log-likelihood partials
+            self._residual_pass(ops, b, Z, part[:b["S"]], b["S"])         # r(z), log-likelihood partials
         G = None
-        if grad_out is not None:
+        if grad_out is not None or gll_out is not None:
             G = b["G"][:, :C]
             ops.gemm_chains(b["Xt"], Z, G, b["work"])     # X^T r                (MFMA, split over N)
-        ops.logistic_finish(G, theta_dc, part, self._inv_s2, float(t), grad_out, logp_out, loglik_out)
+        # (gll_out alone: the finish forms no gradient, only the sums)
+        ops.logistic_finish(G if grad_out is not None else None, theta_dc, part, self._inv_s2, float(t), grad_out, logp_out,
+                            loglik_out)
         if gll_out is not None:
-            if G is None:
-                raise ValueError("gll_out needs grad_out (the likelihood gradient is formed for it)")
             gll_out.copy_(G)
 
     def bk_retemper(self, theta_dc, gll, loglik, t: float, grad_out, logp_out):
@@ -283,6 +305,132 @@ class LogisticRegression(_BuiltinTarget):
                                 dtype=torch.float64, device=th.device)
         self.bk_eval(th, g, lp, t)
         return lp, g.t()
+
+
+class LogisticRegression(_LinearPredictorTarget):
+    """Bayesian logistic regression, y_n ~ Bernoulli(sigmoid(x_n . theta)), theta ~ N(0, s^2 I)
+    (BASELINE.json config 5; no reference counterpart).  The gradient for ALL chains is two
+    fp64 MFMA GEMMs -- Z = X @ Theta (N x C) and G = X^T @ (y - sigmoid(Z)) (D x C) -- with one
+    elementwise pass in between; also a batched LogPriorLikelihoodModel (typing.py:37-42) with
+    a likelihood temperature for smc.py's annealing."""
+
+    _kind = "logistic"
+
+    def __init__(self, X, y, prior_scale: float = 1.0, ops=None):
+        super().__init__(X, prior_scale, ops)
+        self._y_host = torch.as_tensor(y, dtype=torch.float64).reshape(-1)
+
+    def _row_data(self, device):
+        return {"y": self._y_host.to(device).contiguous()}
+
+    def _residual_epilogue(self, ops, b, theta_dc, Z):
+        ops.gemm_chains_logistic(b["X"], theta_dc, Z, b["y"])        # r = y - sigmoid(X theta)
+
+    def _residual_pass(self, ops, b, Z, part, segments):
+        ops.logistic_residual(Z, b["y"], part, segments)             # r = y - sigmoid(z), log-likelihood partials
+
+
+class GLM(_LinearPredictorTarget):
+    """Bayesian regression with a canonical link, theta ~ N(0, s^2 I), eta_n = x_n . theta (+ offset_n):
+
+        "bernoulli":  y_n ~ Bernoulli(sigmoid(eta_n))           y in [0, 1] (fractions allowed, as LogisticRegression)
+        "binomial":   y_n ~ Binomial(trials_n, sigmoid(eta_n))  0 <= y_n <= trials_n
+        "poisson":    y_n ~ Poisson(exp(eta_n))                 y_n >= 0; ``offset`` = log exposure
+        "gaussian":   y_n ~ Normal(eta_n, noise_sd_n)           ``noise_sd``: a positive scalar or an [N] vector
+
+    The logistic target's structure and kernels: two fp64 MFMA GEMMs with the family's cell rule between them (in the first
+    GEMM's epilogue for a gradient-only evaluation), include/bkhip.h "GLM targets".  ``GLM(X, y, "bernoulli")`` is
+    ``LogisticRegression(X, y)`` bit for bit.  The log likelihood is NORMALISED: the observations' constants (log binomial
+    coefficients, -log y!, the Gaussian's log sqrt(w / 2 pi)), summed exactly and rounded once, are added once per
+    evaluation.  Everything LogisticRegression has (bk_eval with a temperature, bk_retemper, the prior / likelihood
+    split), and ``log_prior_gradient`` / ``log_likelihood_gradient``: TemperedHMC treats a GLM as a split model and allows
+    a ``beta = 0`` rung."""
+
+    _kind = "glm"
+
+    def __init__(self, X, y, family, prior_scale: float = 1.0, *, trials=None, noise_sd=None, offset=None, ops=None):
+        import math
+
+        if family not in _lib.GLM_FAMILIES:
+            raise ValueError(f"family must be one of {_lib.GLM_FAMILIES}; found {family!r}")
+        super().__init__(X, prior_scale, ops)
+        self.family, self._family = family, _lib.GLM_FAMILIES.index(family)
+        N = self._N
+
+        def rows(v, name):
+            v = torch.as_tensor(v, dtype=torch.float64).reshape(-1)
+            if v.numel() != N:
+                raise ValueError(f"{name} must have one entry per row of X ({N}); found {v.numel()}")
+            return v
+
+        y = rows(y, "y")
+        if not bool(torch.isfinite(y).all()):
+            raise ValueError("y must be finite")
+        if trials is not None and family != "binomial":
+            raise ValueError(f"trials belongs to the binomial family, not to {family!r}")
+        if noise_sd is not None and family != "gaussian":
+            raise ValueError(f"noise_sd belongs to the gaussian family, not to {family!r}")
+        aux, consts = None, []
+        if family == "bernoulli":
+            if bool(((y < 0) | (y > 1)).any()):
+                raise ValueError("bernoulli: y must lie in [0, 1]")
+        elif family == "binomial":
+            if trials is None:
+                raise ValueError("binomial: trials is required")
+            aux = rows(trials, "trials")
+            if not bool(torch.isfinite(aux).all()):
+                raise ValueError("binomial: trials must be finite")
+            if bool(((y < 0) | (y > aux)).any()):
+                raise ValueError("binomial: y must satisfy 0 <= y <= trials")
+            consts = [math.lgamma(m + 1.0) - math.lgamma(v + 1.0) - math.lgamma(m - v + 1.0)
+                      for v, m in zip(y.tolist(), aux.tolist())]
+        elif family == "poisson":
+            if bool((y < 0).any()):
+                raise ValueError("poisson: y must be >= 0")
+            consts = [-math.lgamma(v + 1.0) for v in y.tolist()]
+        else:
+            if noise_sd is None:
+                raise ValueError("gaussian: noise_sd is required")
+            sd = torch.as_tensor(noise_sd, dtype=torch.float64).reshape(-1)
+            if sd.numel() == 1:
+                sd = sd.expand(N)
+            sd = rows(sd, "noise_sd")
+            if not bool((torch.isfinite(sd) & (sd > 0)).all()):
+                raise ValueError("gaussian: noise_sd must be positive and finite")
+            aux = 1.0 / (sd * sd)  # precision w_n
+            log2pi = math.log(2.0 * math.pi)
+            consts = [0.5 * (math.log(w) - log2pi) for w in aux.tolist()]
+        if offset is not None:
+            offset = rows(offset, "offset")
+            if not bool(torch.isfinite(offset).all()):
+                raise ValueError("offset must be finite")
+        self._y_host, self._aux_host, self._off_host = y, aux, offset
+        self._ll_const = float(math.fsum(consts))  # the double nearest the exact sum of the per-observation constants
+
+    def _row_data(self, device):
+        mv = lambda v: None if v is None else v.to(device).contiguous()  # noqa: E731
+        return {"y": mv(self._y_host), "aux": mv(self._aux_host), "off": mv(self._off_host)}
+
+    def _residual_epilogue(self, ops, b, theta_dc, Z):
+        ops.gemm_chains_glm(b["X"], theta_dc, Z, self._family, b["y"], b["aux"], b["off"])
+
+    def _residual_pass(self, ops, b, Z, part, segments):
+        ops.glm_residual(Z, self._family, b["y"], b["aux"], b["off"], part, segments)
+
+    # the two parts TemperedHMC tempers separately (a split model: beta = 0 is allowed)
+    def log_prior_gradient(self, Theta):
+        """-> (log prior (C,), its gradient (C, D)): -|theta|^2 / (2 s^2) and -theta / s^2."""
+        return self.log_prior(Theta), -(self._inv_s2 * Theta)
+
+    def log_likelihood_gradient(self, Theta):
+        """-> (log likelihood (C,), its gradient (C, D)), untempered, through bk_eval(..., gll_out=)."""
+        th = _as_dc(Theta)
+        f64 = dict(dtype=torch.float64, device=th.device)
+        ld = th.stride(0) if th.shape[0] > 1 else th.shape[1]
+        ll = torch.empty(th.shape[1], **f64)
+        gl = torch.empty_strided(th.shape, (ld, 1), **f64)
+        self.bk_eval(th, None, None, 1.0, ll, gl)  # (gll_out alone: the finish forms no gradient)
+        return ll, gl.t()
 
 
 class CTarget(_BuiltinTarget):

@@ -17,8 +17,8 @@ CSRC = os.path.join(HERE, "csrc")
 OUT_DIR = os.path.join(HERE, "bayes_kit_amd", "lib")
 OBJ_DIR = os.path.join(HERE, "build")
 LIB = os.path.join(OUT_DIR, "libbkhip.so")
-SOURCES = ["bk_rng.hip", "bk_integrator.hip", "bk_targets.hip", "bk_targets_gauss_lanes.hip", "bk_diag.hip", "bk_dr.hip", "bk_dense.hip", "bk_smc.hip", "bk_resample.hip", "bk_mala.hip", "bk_sort.hip", "bk_fft.hip", "bk_ess_multi.hip", "bk_stretch.hip", "bk_cov.hip", "bk_temper.hip", "bk_hist.hip", "bk_energy.hip"]
-HEADERS = ["bk_common.hpp", "bk_ess_tile.hpp", "bk_rng.hpp", "bk_lanes.hpp", "bk_elementwise.hpp", "bk_mala_step.hpp", "bk_tile_kernels.hpp", "bk_mem_policy.hpp", "ziggurat_tables.inc", os.path.join("..", "..", "include", "bkhip.h"),
+SOURCES = ["bk_rng.hip", "bk_integrator.hip", "bk_targets.hip", "bk_targets_gauss_lanes.hip", "bk_diag.hip", "bk_dr.hip", "bk_dense.hip", "bk_smc.hip", "bk_resample.hip", "bk_mala.hip", "bk_sort.hip", "bk_fft.hip", "bk_ess_multi.hip", "bk_stretch.hip", "bk_cov.hip", "bk_temper.hip", "bk_hist.hip", "bk_energy.hip", "bk_glm.hip"]
+HEADERS = ["bk_common.hpp", "bk_ess_tile.hpp", "bk_rng.hpp", "bk_lanes.hpp", "bk_elementwise.hpp", "bk_mala_step.hpp", "bk_tile_kernels.hpp", "bk_mem_policy.hpp", "bk_glm.hpp", "ziggurat_tables.inc", os.path.join("..", "..", "include", "bkhip.h"),
            os.path.join("..", "..", "include", "bkhip_math.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-Wall", "-Wno-unused-function"]

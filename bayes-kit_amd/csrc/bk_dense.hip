@@ -17,6 +17,7 @@
 // a panel of X (same chains, different rows of M) are placed on the same XCD back to back
 // so the panel is fetched from HBM once and then served by that XCD's L2.
 #include "bk_common.hpp"
+#include "bk_glm.hpp"
 
 namespace {
 
@@ -99,11 +100,14 @@ __device__ __forceinline__ void store_panels(DenseLds& lds, int buf, const doubl
 // EPI 1: the result leaves as  y_rows[r] - sigmoid(z)  (the logistic regression's residual, the arithmetic of
 // k_logistic_residual): the elementwise pass between the target's two GEMMs rides on the first one's epilogue --
 // its exp and division run on the vector pipe while the CU's other workgroup keeps the matrix pipe busy.
+// EPI >= BK_EPI_GLM0 (bk_glm_epi(family, offset)): the same for the GLM families -- the result leaves as bk_glm_cell's
+// residual of the row's y_rows[r], aux_rows[r] (trials / precision) and off_rows[r], the arithmetic of k_glm_residual.
 template <bool FULL, int EPI>
 __global__ __launch_bounds__(256, 2) void k_dense_apply(const double* M, i64 ldm, const double* X, double* Y,
                                                         i64 ld, i64 ldy, i64 C, i64 R, i64 Dtot, int row_blocks,
                                                         int chain_blocks, i64 k_chunk, i64 slab_elems,
-                                                        const double* y_rows) {
+                                                        const double* y_rows, const double* aux_rows,
+                                                        const double* off_rows) {
   __shared__ DenseLds lds;
   // split-K: blockIdx.y owns the inner-dimension range [k_lo, k_hi) and its own output slab
   const i64 k_lo = (i64)blockIdx.y * k_chunk;
@@ -187,6 +191,13 @@ __global__ __launch_bounds__(256, 2) void k_dense_apply(const double* M, i64 ldm
             const double p = out >= 0.0 ? 1.0 / (1.0 + e) : e / (1.0 + e);
             out = y_rows[r] - p;
           }
+          if constexpr (EPI >= BK_EPI_GLM0) {
+            constexpr int FAM = (EPI - BK_EPI_GLM0) / 2;
+            constexpr bool OFF = ((EPI - BK_EPI_GLM0) & 1) != 0;
+            constexpr bool AUX = FAM == BK_GLM_BINOMIAL || FAM == BK_GLM_GAUSSIAN;
+            double term;
+            out = bk_glm_cell<FAM, OFF, false>(out, y_rows[r], AUX ? aux_rows[r] : 0.0, OFF ? off_rows[r] : 0.0, term);
+          }
           if (k_chunk >= 0) Y[r * ldy + c] = out;
         }
       }
@@ -231,7 +242,8 @@ namespace {
 
 // one GEMM launch (+ one for a last partial block of rows): `out` rows of pitch ldy, split-K slab q at out + q * slab_elems
 static int gemm_block(const double* A, i64 lda, i64 R, i64 K, const double* X, i64 ldx, double* out, i64 ldy, i64 C,
-                      i64 S, i64 k_chunk, i64 slab_elems, void* stream, const double* y_rows) {
+                      i64 S, i64 k_chunk, i64 slab_elems, void* stream, const double* y_rows, int epi = -1,
+                      const double* aux_rows = nullptr, const double* off_rows = nullptr) {
   i64 rb = bk_cdiv(R, BM), cb = bk_cdiv(C, BN);
   i64 per = (cb + 7) / 8;
   if (per * 8 * rb > 0x7fffffff) return BK_E_ARG;
@@ -246,23 +258,41 @@ static int gemm_block(const double* A, i64 lda, i64 R, i64 K, const double* X, i
   if (R_full > 0) {
     const i64 rbf = R_full / BM;
     const dim3 grid((unsigned)(per * 8 * rbf), (unsigned)S);
-    if (y_rows)
+    if (epi >= BK_EPI_GLM0) {
+#define BK_GLM_FULL(FAM, OFF)                                                                                              \
+  k_dense_apply<true, bk_glm_epi(FAM, OFF)><<<grid, dim3(256), 0, st>>>(A, lda, X, out, ldx, ldy, C, R_full, K, (int)rbf, \
+                                                                        (int)cb, k_chunk, slab_elems, y_rows, aux_rows,   \
+                                                                        off_rows)
+      BK_GLM_DISPATCH((epi - BK_EPI_GLM0) / 2, (epi - BK_EPI_GLM0) & 1, BK_GLM_FULL);
+#undef BK_GLM_FULL
+    } else if (y_rows)
       k_dense_apply<true, 1><<<grid, dim3(256), 0, st>>>(A, lda, X, out, ldx, ldy, C, R_full, K, (int)rbf, (int)cb,
-                                                         k_chunk, slab_elems, y_rows);
+                                                         k_chunk, slab_elems, y_rows, nullptr, nullptr);
     else
       k_dense_apply<true, 0><<<grid, dim3(256), 0, st>>>(A, lda, X, out, ldx, ldy, C, R_full, K, (int)rbf, (int)cb,
-                                                         k_chunk, slab_elems, nullptr);
+                                                         k_chunk, slab_elems, nullptr, nullptr, nullptr);
   }
   if (R_full < R) {
     // rows [R_full, R): its split-K slabs sit at the same row offset inside each slab of R rows
     const i64 rr = R - R_full, rbr = bk_cdiv(rr, BM);
     const dim3 grid((unsigned)(per * 8 * rbr), (unsigned)S);
-    if (y_rows)
+    if (epi >= BK_EPI_GLM0) {
+      // the per-row arrays all advance with the rows: y, and aux / offset where the family has them
+      const double* aux_r = aux_rows ? aux_rows + R_full : nullptr;
+      const double* off_r = off_rows ? off_rows + R_full : nullptr;
+#define BK_GLM_PART(FAM, OFF)                                                                                            \
+  k_dense_apply<false, bk_glm_epi(FAM, OFF)><<<grid, dim3(256), 0, st>>>(A + R_full * lda, lda, X, out + R_full * ldy,  \
+                                                                         ldx, ldy, C, rr, K, (int)rbr, (int)cb, k_chunk, \
+                                                                         slab_elems, y_rows + R_full, aux_r, off_r)
+      BK_GLM_DISPATCH((epi - BK_EPI_GLM0) / 2, (epi - BK_EPI_GLM0) & 1, BK_GLM_PART);
+#undef BK_GLM_PART
+    } else if (y_rows)
       k_dense_apply<false, 1><<<grid, dim3(256), 0, st>>>(A + R_full * lda, lda, X, out + R_full * ldy, ldx, ldy, C, rr, K,
-                                                          (int)rbr, (int)cb, k_chunk, slab_elems, y_rows + R_full);
+                                                          (int)rbr, (int)cb, k_chunk, slab_elems, y_rows + R_full, nullptr,
+                                                          nullptr);
     else
       k_dense_apply<false, 0><<<grid, dim3(256), 0, st>>>(A + R_full * lda, lda, X, out + R_full * ldy, ldx, ldy, C, rr, K,
-                                                          (int)rbr, (int)cb, k_chunk, slab_elems, nullptr);
+                                                          (int)rbr, (int)cb, k_chunk, slab_elems, nullptr, nullptr, nullptr);
   }
   BK_RETURN_LAUNCH_STATUS();
 }
@@ -293,7 +323,8 @@ static i64 gemm_slabs(i64 R, i64 K, i64* k_chunk_out) {
 }
 
 static int gemm_launch(const double* A, i64 lda, i64 R, i64 K, const double* X, i64 ldx, double* Y, i64 ldy, i64 C,
-                       double* work, i64 work_elems, void* stream, const double* y_rows = nullptr) {
+                       double* work, i64 work_elems, void* stream, const double* y_rows = nullptr, int epi = -1,
+                       const double* aux_rows = nullptr, const double* off_rows = nullptr) {
   if (!A || !X || !Y || C < 0 || R < 0 || K < 0 || lda < K) return BK_E_ARG;
   if (ldx < C || ldy < C) return BK_E_ALIGN;
   if (C == 0 || R == 0) return BK_OK;
@@ -313,7 +344,7 @@ static int gemm_launch(const double* A, i64 lda, i64 R, i64 K, const double* X, 
     }
     BK_RETURN_LAUNCH_STATUS();
   }
-  return gemm_block(A, lda, R, K, X, ldx, Y, ldy, C, 1, K, 0, stream, y_rows);
+  return gemm_block(A, lda, R, K, X, ldx, Y, ldy, C, 1, K, 0, stream, y_rows, epi, aux_rows, off_rows);
 }
 
 }  // namespace
@@ -342,6 +373,15 @@ int bk_gemm_chains_logistic(const double* A, int64_t lda, int64_t R, int64_t K, 
                             double* Y, int64_t ldy, int64_t C, const double* y_rows, void* stream) {
   if (!y_rows) return BK_E_ARG;
   return gemm_launch(A, lda, R, K, X, ldx, Y, ldy, C, nullptr, 0, stream, y_rows);
+}
+
+int bk_gemm_chains_glm(const double* A, int64_t lda, int64_t R, int64_t K, const double* X, int64_t ldx, double* Y,
+                       int64_t ldy, int64_t C, int family, const double* y_rows, const double* aux_rows,
+                       const double* offset_rows, void* stream) {
+  if (bk_glm_check(family, y_rows, aux_rows) != BK_OK) return BK_E_ARG;
+  // (like the logistic entry point: never a split of K, no work buffer -- the epilogue needs the whole sum)
+  return gemm_launch(A, lda, R, K, X, ldx, Y, ldy, C, nullptr, 0, stream, y_rows, bk_glm_epi(family, offset_rows != nullptr),
+                     aux_rows, offset_rows);
 }
 
 int bk_dot_columns(const double* x, const double* y, int64_t ld, double scale, double* out, int64_t C, int64_t D,

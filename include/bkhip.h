@@ -931,6 +931,61 @@ int bk_logistic_finish(const double* G, const double* theta, int64_t ld, const d
                        int64_t segments, double inv_prior_var, double t, double* grad, double* logp,
                        double* loglik, int64_t C, int64_t D, void* stream);
 
+/* GLM targets: regression with a canonical link (no reference counterpart), with the logistic target's structure --
+ * one linear predictor, one cell-wise map between the two GEMMs, a residual that is y minus a mean.  Per cell, from
+ * z = (X_data Theta)[n][c], the row's y[n], the row's aux[n] (BINOMIAL: trials m; GAUSSIAN: precision w = 1 / sd^2;
+ * BERNOULLI, POISSON: no aux) and the row's offset[n] (optional), every line ONE rounded fp64 operation per
+ * operator, in this association (the build does not contract):
+ *
+ *     eta = offset ? z + o : z                       (offset NULL: no load, no addition)
+ *     BERNOULLI: e = exp(-|eta|); p = eta >= 0 ? 1/(1+e) : e/(1+e);  r = y - p
+ *                term = y*eta - ((eta > 0 ? eta : 0) + log1p(e))
+ *     BINOMIAL:  e, p as above;                                      r = y - a*p
+ *                term = y*eta - a*((eta > 0 ? eta : 0) + log1p(e))
+ *     POISSON:   mu = exp(eta);                                      r = y - mu;   term = y*eta - mu
+ *     GAUSSIAN:  d = y - eta;                                        r = a*d;      term = -0.5*(r*d)
+ *
+ * BERNOULLI without an offset is bk_logistic_residual's / bk_gemm_chains_logistic's arithmetic: the same bits.  `term`
+ * leaves out the observation's normalising constant (log binomial coefficient, -log y!, 0.5 (log w - log 2 pi)): the
+ * caller adds its sum once (bk.GLM carries it as one more row of `part` for bk_logistic_finish to sum).
+ * No clamping; a non-finite eta gives what IEEE gives (a: 1 for BERNOULLI, m for BINOMIAL; w finite and > 0):
+ *
+ *     BERNOULLI / BINOMIAL     r        term, y = 0          term, y > 0
+ *       eta = +inf             y - a    NaN  (0 * inf)        NaN  (inf - inf)
+ *       eta = -inf             y        NaN  (0 * -inf)       -inf
+ *       eta = NaN              NaN      NaN                   NaN
+ *     POISSON
+ *       eta = +inf             -inf     NaN  (0 * inf - inf)  NaN  (inf - inf)
+ *       eta > 709.78 (finite)  -inf     -inf                  -inf          (exp overflows)
+ *       eta = -inf             y        NaN  (0 * -inf)       -inf
+ *       eta = NaN              NaN      NaN                   NaN
+ *     GAUSSIAN
+ *       eta = +inf             -inf     -inf                  -inf
+ *       eta = -inf             +inf     -inf                  -inf
+ *       eta = NaN              NaN      NaN                   NaN
+ *
+ * A segment sum with a NaN term is NaN; one with -inf terms and no NaN is -inf.  Other cells and other segment sums
+ * keep their bits.
+ *
+ *   bk_gemm_chains_glm: bk_gemm_chains whose result leaves as r (the cell rule in the GEMM's epilogue; never a split
+ *       of K, no work buffer).  Same values as the GEMM followed by bk_glm_residual(part = NULL); degenerate sizes as
+ *       bk_gemm_chains (K = 0: the cell rule of z = 0).
+ *   bk_glm_residual: Z[n*ldz + c] <- r in place, and part[s*C + c] = the left-to-right sum of `term` over the s-th of
+ *       `segments` blocks of ceil(max(N, 1) / segments) observations (blocks past the data: exactly +0.0).  part NULL:
+ *       gradient only -- no log1p, nothing stored to part.
+ *   bk_logistic_finish serves every family (grad = t*G + (-(inv_prior_var*theta)), the left-to-right sum of part).
+ * BK_E_ARG, decided before any launch: an unknown family, aux NULL for BINOMIAL / GAUSSIAN, aux given for BERNOULLI /
+ * POISSON, a NULL y (y_rows), segments outside [1, 65535], and what bk_gemm_chains / bk_logistic_residual refuse. */
+#define BK_GLM_BERNOULLI 0
+#define BK_GLM_BINOMIAL 1
+#define BK_GLM_POISSON 2
+#define BK_GLM_GAUSSIAN 3
+int bk_gemm_chains_glm(const double* A, int64_t lda, int64_t R, int64_t K, const double* X, int64_t ldx, double* Y,
+                       int64_t ldy, int64_t C, int family, const double* y_rows, const double* aux_rows,
+                       const double* offset_rows, void* stream);
+int bk_glm_residual(double* Z, int64_t ldz, int family, const double* y, const double* aux, const double* offset,
+                    double* part, int64_t N, int64_t C, int64_t segments, void* stream);
+
 /* out[c] = scale * sum_d x[d*ld + c] * y[d*ld + c]  (kinetic energy 0.5 * rho . (M rho)). */
 int bk_dot_columns(const double* x, const double* y, int64_t ld, double scale, double* out,
                    int64_t C, int64_t D, void* stream);
