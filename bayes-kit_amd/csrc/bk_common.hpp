@@ -41,6 +41,38 @@ static inline i64 bk_distinct_arrays(std::initializer_list<const void*> arrays) 
   return n;
 }
 
+// ---- the shapes of the MALA step kernels (k_mala_step, k_mala_step_sep; bk_mala_step_supported) ---------------------------
+// Every global access of those kernels is a buffer instruction: a 32-bit per-thread byte offset plus a 32-bit scalar slot
+// offset, against a descriptor whose num_records has 32 bits too.  The descriptor's range check is the kernels' only edge
+// handling, and it sees an offset only as it was FORMED: one that wrapped lands back inside num_records and is a store into
+// live rows.  A thread forms the offsets of rows r + 64 e, r <= 63, e <= E - 1 WHATEVER D is, so "the arrays are small" is
+// not enough (D = 32, ld = 4,400,000: a 1.1 GB array, row 127 at byte 4.47e9).  The forms, each with the 16 bytes of the
+// access added, all below 2^32:
+//   nbytes = ((D - 1) ld + C) 8                                      num_records
+//   ((r ld + c) 8) + e 64 ld 8 + 16,  c <= C - 2                     loads, and the stores of chain pairs below C
+//   nbytes + e 64 ld 8 + 16                                          the stores of a ragged last block's pairs past C
+// and for the next draw's normals (chain cc <= C - 1 of zt[C][ldz], lane <= 63, E/2 pieces of 1 KiB):
+//   zbytes = ((C - 1) ldz + D) 8,    cc ldz 8 + 16 * 63 + 1024 (E/2 - 1) + 16
+// The former bound D ld < 2^28 (arrays below 2 GiB) is kept beside them: nothing larger than before is accepted.
+static inline int bk_mala_step_slots(i64 D) { return D <= 128 ? 2 : D <= 256 ? 4 : D <= 512 ? 8 : 16; }
+
+static inline bool bk_mala_step_shape_ok(i64 C, i64 D, i64 ld) {
+  const i64 lim = (i64)1 << 32;
+  if (!(C > 0 && D > 0 && D <= 1024 && C % 2 == 0 && ld % 2 == 0 && ld >= C)) return false;
+  if (ld >= ((i64)1 << 28) || D * ld >= ((i64)1 << 28)) return false;
+  const i64 slots = (bk_mala_step_slots(D) - 1) * 64 * ld * 8;
+  const i64 nbytes = ((D - 1) * ld + C) * 8;
+  return ((63 * ld + (C - 2)) * 8) + slots + 16 < lim && nbytes + slots + 16 < lim;
+}
+
+// (C, D already passed bk_mala_step_shape_ok; ldz >= D)
+static inline bool bk_mala_step_normals_ok(i64 C, i64 D, i64 ldz) {
+  const i64 lim = (i64)1 << 32;
+  if (ldz >= lim) return false;
+  return ((C - 1) * ldz + D) * 8 < lim &&
+         (C - 1) * ldz * 8 + 16 * 63 + 1024 * (bk_mala_step_slots(D) / 2 - 1) + 16 < lim;
+}
+
 // Index of the calling wavefront inside its workgroup AS A SCALAR: threadIdx.x / 64 is the same for
 // all 64 lanes, but the compiler only knows that if told -- otherwise every loop bound, row guard and
 // address derived from it is per-lane vector work (selects, 64-bit VGPR address math).

@@ -914,7 +914,7 @@ int bk_mala_logq(const double* theta, const double* grad, const double* theta_pr
   if (!theta || !grad || !theta_prop || !grad_prop || !lp_forward || !lp_reverse || C < 0 || D < 0)
     return BK_E_ARG;
   if (ld < C) return BK_E_ALIGN;
-  if (C == 0) return BK_OK;
+  if (C == 0 || D == 0) return BK_OK;
   k_mala_logq<false><<<dim3((unsigned)bk_cdiv(C, BK_WAVE)), dim3(RED_BLOCK), 0, bk_stream(stream)>>>(
       theta, grad, theta_prop, grad_prop, ld, eps, lp_forward, lp_reverse, C, D, nullptr);
   BK_RETURN_LAUNCH_STATUS();

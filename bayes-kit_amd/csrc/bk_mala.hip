@@ -309,8 +309,8 @@ __global__ __launch_bounds__(MS_THREADS) void k_mala_step(
 extern "C" {
 
 int bk_mala_step_supported(int64_t C, int64_t D, int64_t ld) {
-  // 32-bit byte offsets inside every array, with headroom for the slot offsets: arrays < 2 GiB
-  return (C > 0 && D > 0 && D <= 1024 && C % 2 == 0 && ld % 2 == 0 && ld >= C && D * ld < ((int64_t)1 << 28)) ? 1 : 0;
+  // every byte offset the kernel forms fits 32 bits with the access width added (bk_common.hpp: bk_mala_step_shape_ok)
+  return bk_mala_step_shape_ok(C, D, ld) ? 1 : 0;
 }
 
 }  // extern "C"
@@ -330,6 +330,7 @@ int mala_step_launch(const double* theta, double* theta_out, double* grad, doubl
       !bk_aligned16(grad_prop))
     return BK_E_ALIGN;
   if (zt_next && (ldz < D || ldz % 2 != 0 || !bk_aligned16(zt_next))) return BK_E_ALIGN;
+  if (zt_next && !bk_mala_step_normals_ok(C, D, ldz)) return BK_E_ALIGN;
   hipStream_t s = bk_stream(stream);
   dim3 grid((unsigned)bk_cdiv(C, MS_CHAINS)), block(MS_THREADS);
   const bool nt = bk_streams_past_llc(6 * C * D);

@@ -263,10 +263,11 @@ static int mala_step_sep_launch(const double* theta, double* theta_out, double* 
   if (PC && !precond) return BK_E_ARG;
   if (!theta || !theta_out || !theta_prop || !lp || !lp_prop || !log_u || C < 0 || D < 0) return BK_E_ARG;
   if (C == 0 || D == 0) return BK_OK;
-  // 32-bit byte offsets inside every array, with headroom for the slot offsets (bk_mala_step_supported)
-  if (!(D <= 1024 && C % 2 == 0 && ld % 2 == 0 && ld >= C && D * ld < ((int64_t)1 << 28))) return BK_E_ALIGN;
+  // every byte offset the kernel forms fits 32 bits with the access width added (bk_mala_step_supported's test)
+  if (!bk_mala_step_shape_ok(C, D, ld)) return BK_E_ALIGN;
   if (!bk_aligned16(theta) || !bk_aligned16(theta_out) || !bk_aligned16(theta_prop)) return BK_E_ALIGN;
   if (zt_next && (ldz < D || ldz % 2 != 0 || !bk_aligned16(zt_next))) return BK_E_ALIGN;
+  if (zt_next && !bk_mala_step_normals_ok(C, D, ldz)) return BK_E_ALIGN;
   hipStream_t s = bk_stream(stream);
   constexpr int P = 8;  // chain pairs per workgroup (the note on PAIRS above)
   const bool nt = bk_streams_past_llc(4 * C * D);

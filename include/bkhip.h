@@ -585,7 +585,10 @@ int bk_mala_single_draw(int rng_kind, uint64_t* state, int64_t ldr, double* thet
                         int64_t D, int have_prop, double seq, void* stream);
 
 /* lp_forward[c] = (-0.25/eps) * |(theta_prop - theta) - eps*grad|^2       mala.py:50-52
- * lp_reverse[c] = (-0.25/eps) * |(theta - theta_prop) - eps*grad_prop|^2   mala.py:53,68-79 */
+ * lp_reverse[c] = (-0.25/eps) * |(theta - theta_prop) - eps*grad_prop|^2   mala.py:53,68-79
+ * Sums over four contiguous quarters of ceil(D/4) rows, each in order of d, combined ((p0+p1)+p2)+p3.
+ * BK_E_ARG: a NULL array, C < 0 or D < 0; BK_E_ALIGN: ld < C.  C == 0 or D == 0: BK_OK, nothing launched and
+ * nothing written (bk_mala_logq_precond the same). */
 int bk_mala_logq(const double* theta, const double* grad, const double* theta_prop,
                  const double* grad_prop, int64_t ld, double eps, double* lp_forward,
                  double* lp_reverse, int64_t C, int64_t D, void* stream);
@@ -617,8 +620,16 @@ int bk_mala_logq_precond(const double* theta, const double* grad, const double* 
  * generator's write of zt (8*D) a draw moves 88*D bytes per chain.
  * The per-chain sums run per thread over rows r, r+64, ..., then over a fixed xor tree of the 8
  * rows of a wavefront, then over the 8 wavefronts in order: an order that depends on D only.
- * Supported shapes (bk_mala_step_supported): D <= 1024, C and ld even, 16-byte aligned arrays;
- * otherwise BK_E_ALIGN -- callers then use bk_mala_logq + bk_mh_accept + bk_select_columns. */
+ * Supported shapes (bk_mala_step_supported): 0 < D <= 1024, C and ld even, ld >= C, 16-byte aligned arrays,
+ * and every byte offset the kernel forms below 2^32 with the 16 bytes of an access added.  The kernel
+ * addresses with 32-bit offsets against a 32-bit range check, and a thread forms the offsets of rows
+ * r + 64 e (r <= 63, e < E; E = 2, 4, 8, 16 for D <= 128, 256, 512, 1024) whatever D is, so with
+ * S = (E - 1) * 64 * ld * 8:
+ *     ((63*ld + C - 2) * 8) + S + 16 < 2^32   and   (((D - 1)*ld + C) * 8) + S + 16 < 2^32,
+ * and D * ld < 2^28 as before.  With zt_next also ((C - 1)*ldz + D) * 8 < 2^32 and
+ * (C - 1)*ldz*8 + 16*63 + 1024*(E/2 - 1) + 16 < 2^32 (bk_mala_step_supported does not see ldz; ldz <= 64 E
+ * never adds a restriction).  Otherwise BK_E_ALIGN, decided before any HIP call -- callers then use
+ * bk_mala_logq + bk_mh_accept + bk_select_columns.  C == 0 or D == 0: BK_OK, nothing launched. */
 int bk_mala_step_supported(int64_t C, int64_t D, int64_t ld);
 int bk_mala_step(const double* theta, double* theta_out, double* grad, double* theta_prop,
                  const double* grad_prop, int64_t ld, double* lp, const double* lp_prop,

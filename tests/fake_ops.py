@@ -272,7 +272,13 @@ class FakeOps:
         lp_reverse.numpy()[...] = k * sr
 
     def mala_step_supported(self, C, D, ld):
-        return C % 2 == 0 and ld % 2 == 0 and 0 < D <= 1024
+        """bk_mala_step_supported (include/bkhip.h): even C and ld, D <= 1024, and every 32-bit byte offset the step kernel
+        forms -- rows up to 64 E - 1 whatever D is -- below 2**32 with the 16 bytes of an access added."""
+        if not (C > 0 and 0 < D <= 1024 and C % 2 == 0 and ld % 2 == 0 and ld >= C and D * ld < 2 ** 28):
+            return False
+        E = 2 if D <= 128 else 4 if D <= 256 else 8 if D <= 512 else 16
+        slots = (E - 1) * 64 * ld * 8
+        return ((63 * ld + C - 2) * 8 + slots + 16 < 2 ** 32) and (((D - 1) * ld + C) * 8 + slots + 16 < 2 ** 32)
 
     def mala_step_gaussian(self, lam, theta, theta_out, theta_prop, lp, lp_prop, log_u, zt_next, eps, sqrt2eps, mask, ret, count):
         self._count("mala_step_gaussian")

@@ -41,14 +41,15 @@ def step_sum(x):
 
 def _residuals(th, g, thp, gp, eps, pd):
     """-> the forward / reverse terms summed per chain: (x*x) plain, (x*x)*(1/v) with x = .. - eps*(v*grad) preconditioned."""
-    if pd is None:
-        xf = (thp - th) - eps * g
-        xr = (th - thp) - eps * gp
-        return xf * xf, xr * xr
-    v, iv = pd[0][:, None], pd[2][:, None]
-    xf = (thp - th) - eps * (v * g)
-    xr = (th - thp) - eps * (v * gp)
-    return (xf * xf) * iv, (xr * xr) * iv
+    with np.errstate(invalid="ignore", over="ignore"):  # (a non-finite input follows IEEE arithmetic, as on the device)
+        if pd is None:
+            xf = (thp - th) - eps * g
+            xr = (th - thp) - eps * gp
+            return xf * xf, xr * xr
+        v, iv = pd[0][:, None], pd[2][:, None]
+        xf = (thp - th) - eps * (v * g)
+        xr = (th - thp) - eps * (v * gp)
+        return (xf * xf) * iv, (xr * xr) * iv
 
 
 class MalaAdaptFakeOps(AdaptFakeOps):
@@ -63,6 +64,8 @@ class MalaAdaptFakeOps(AdaptFakeOps):
 
     # -- proposal densities ---------------------------------------------------------------------------------------------
     def _logq(self, theta, grad, theta_prop, grad_prop, eps, lp_forward, lp_reverse, pd):
+        if theta.shape[0] == 0 or theta.shape[1] == 0:  # C == 0 or D == 0: BK_OK, nothing launched, nothing written
+            return
         tf, tr = _residuals(theta.numpy(), grad.numpy(), theta_prop.numpy(), grad_prop.numpy(), eps, pd)
         k = -0.25 / eps
         lp_forward.numpy()[...] = k * quarter_sum(tf)
