@@ -1116,34 +1116,29 @@ class TorchModel:
         whole-draw HMC kernel).  Otherwise: a warning naming the unsupported node, and autograd as before."""
         import warnings
 
-        from . import trace
+        from . import trace, trace_chain, trace_lanes
 
-        form, head = "elementwise", 0
-        try:
-            src, params, info = trace.term_source(self._fn, self._D, "dc" if self._dc else "cd")
-        except trace.Unsupported as e:
-            # not separable: a head-plus-sums (hierarchical) density?  (trace_lanes.py; the reference's (C, D) layout only)
+        # separable; else head-plus-sums (hierarchical); else coordinates coupled through shifted slices (AR(1), random walks,
+        # state-space models).  The last two read the reference's (C, D) layout only: `refusal` is what the other one gets.
+        refused = []
+        for form, label, tracer, refusal in (
+                ("elementwise", "as a sum over coordinates", lambda: trace.term_source(self._fn, self._D, "dc" if self._dc else "cd"), None),
+                ("lanes", "as head coordinates plus sums over rows", lambda: trace_lanes.lanes_source(self._fn, self._D),
+                 "head-plus-sums densities are traced in the (C, D) layout only"),
+                ("chain", "as sums over shifted slices", lambda: trace_chain.chain_source(self._fn, self._D),
+                 "traced in the (C, D) layout only")):
             try:
-                if self._dc:
-                    raise trace.Unsupported("head-plus-sums densities are traced in the (C, D) layout only")
-                from . import trace_lanes
-
-                src, head, params, info = trace_lanes.lanes_source(self._fn, self._D)
-                form = "lanes"
-            except trace.Unsupported as e2:
-                # coordinates coupled through shifted slices (AR(1), random walks, state-space models)?  -> the per-chain form
-                try:
-                    if self._dc:
-                        raise trace.Unsupported("traced in the (C, D) layout only")
-                    from . import trace_chain
-
-                    src, params, info = trace_chain.chain_source(self._fn, self._D)
-                    form = "chain"
-                except trace.Unsupported as e3:
-                    self.compile_note = (f"as a sum over coordinates: {e}; as head coordinates plus sums over rows: {e2}; "
-                                         f"as sums over shifted slices: {e3}")
-                    warnings.warn(f"TorchModel(compile=True): not traceable ({self.compile_note}); keeping autograd", stacklevel=3)
-                    return
+                if self._dc and refusal:
+                    raise trace.Unsupported(refusal)
+                src, *head, params, info = tracer()   # (lanes_source alone returns a head count, second)
+                head = head[0] if head else 0
+                break
+            except trace.Unsupported as e:
+                refused.append(f"{label}: {e}")
+        else:
+            self.compile_note = "; ".join(refused)
+            warnings.warn(f"TorchModel(compile=True): not traceable ({self.compile_note}); keeping autograd", stacklevel=3)
+            return
         dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
         p = None if params is None else params.to(dev)
         stage = info.get("stage", "auto") if form == "chain" else "auto"

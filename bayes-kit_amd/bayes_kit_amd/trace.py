@@ -15,6 +15,10 @@ along the coordinate axis (shape (D,) / (1, D) for the (C, D) layout, (D, 1) for
 ``.size()`` of the coordinate axis; ``torch.broadcast_tensors``.  That set covers ``torch.distributions`` log_prob bodies such as
 Normal, StudentT, Laplace, Cauchy, Logistic with constant parameters (argument validation is data-dependent control flow, so it
 is switched off while the function is being read).
+
+This module also owns what the other two tracers (``trace_lanes.py``, ``trace_chain.py``) read a function with: the one
+``torch.fx`` graph walk (``walk``), the operation tables, and the argument handling every ``apply`` starts with (``plumbing``,
+``sum_args``, ``normalise``, ``piecewise_rewrite``).  Its own IR (``_E``) and emitter (``_Emit``) stay separate from their DAG.
 """
 from __future__ import annotations
 
@@ -139,6 +143,101 @@ def piecewise_rewrite(name, args, kwargs, where):
     return None
 
 
+def walk(fn, apply, theta, functions=(), methods=()):
+    """The one reading of a function for all three tracers (this module, trace_lanes.py, trace_chain.py): trace it with
+    torch.fx, then evaluate the graph node by node -- the placeholder is `theta`, an attribute is the object itself (classified
+    where it is used: the operation is what an error should name), a call is apply(name, args, kwargs, where) with the name
+    from the tables above plus the tracer's own `functions` / `methods` entries -- and return the value of the output node."""
+    import torch.fx as fx
+
+    try:
+        with no_distribution_validation():
+            gm = fx.symbolic_trace(fn)
+    except Exception as e:  # data-dependent control flow, in-place tricks, ...
+        raise Unsupported(f"torch.fx could not trace the function: {type(e).__name__}: {e}") from e
+    table = {**_function_table(), **dict(functions)}
+    methods = dict(_METHODS, **dict(methods))
+    env, out, n_inputs = {}, None, 0
+    for node in gm.graph.nodes:
+        where = f"node `{node.format_node()}`"
+
+        def val(a):
+            if isinstance(a, (tuple, list)):
+                return type(a)(val(x) for x in a)
+            return env[a] if isinstance(a, fx.Node) else a
+
+        if node.op == "placeholder":
+            n_inputs += 1
+            if n_inputs > 1:
+                raise Unsupported("the function takes more than one argument")
+            env[node] = theta
+        elif node.op == "get_attr":
+            obj = gm
+            for part in node.target.split("."):
+                obj = getattr(obj, part)
+            env[node] = obj
+        elif node.op in ("call_function", "call_method"):
+            name = table.get(node.target) if node.op == "call_function" else methods.get(node.target)
+            if name is None:
+                raise Unsupported(f"{where}: unsupported operation {getattr(node.target, '__name__', node.target)!r}")
+            env[node] = apply(name, [val(a) for a in node.args], {k: val(v) for k, v in node.kwargs.items()}, where)
+        elif node.op == "output":
+            out = val(node.args[0])
+        else:
+            raise Unsupported(f"{where}: unsupported node kind {node.op}")
+    return out
+
+
+# ---- what every tracer's apply() does before its own algebra ------------------------------------------------------------------
+NOT_PLUMBING = object()
+
+
+def plumbing(name, args, where, shape_of):
+    """The operations that move values about without computing: id, broadcast_tensors, indexing a tuple, .shape, .size();
+    NOT_PLUMBING for every other one (indexing a traced value included: that is the tracer's own)."""
+    if name == "id":
+        return args[0]
+    if name == "broadcast_tensors":  # (torch.distributions' broadcast_all): the operands themselves; every operation
+        return tuple(args[0]) if len(args) == 1 and isinstance(args[0], (tuple, list)) else tuple(args)  # broadcasts anyway
+    if name == "getitem" and isinstance(args[0], (tuple, list)) and isinstance(args[1], int):
+        return args[0][args[1]]
+    if name == "getattr":
+        if args[1] == "shape":
+            return shape_of(args[0], where)
+        raise Unsupported(f"{where}: attribute {args[1]!r}")
+    if name == "size":
+        shp = shape_of(args[0], where)
+        return shp if len(args) == 1 else shp[args[1]]
+    return NOT_PLUMBING
+
+
+def sum_args(args, kwargs):
+    """(dim as written, keepdim asked for, a dtype other than float64 asked for) of a sum / mean."""
+    dim = args[1] if len(args) > 1 else kwargs.get("dim", kwargs.get("axis"))
+    return dim, bool(kwargs.get("keepdim", False) or (len(args) > 2 and args[2])), kwargs.get("dtype") not in (None, torch.float64)
+
+
+def one_axis(dim):
+    return dim[0] if isinstance(dim, (list, tuple)) and len(dim) == 1 else dim
+
+
+def normalise(name, args, kwargs, where):
+    """(args, kwargs) with the arguments that only restate a default dropped -- relu(inplace=False), softplus(beta=1,
+    threshold=20) -- and every other keyword argument but clamp's bounds refused."""
+    if name == "relu" and kwargs.get("inplace") is False:
+        kwargs = {}
+    if kwargs and not (name == "softplus" and set(kwargs) <= {"beta", "threshold"}) \
+            and not (name.startswith("clamp") and set(kwargs) <= {"min", "max"}):
+        raise Unsupported(f"{where}: keyword arguments {sorted(kwargs)}")
+    if name == "softplus":
+        beta = kwargs.get("beta", args[1] if len(args) > 1 else 1.0)
+        thr = kwargs.get("threshold", args[2] if len(args) > 2 else 20.0)
+        if float(beta) != 1.0 or float(thr) != 20.0:
+            raise Unsupported(f"{where}: softplus with beta / threshold other than the defaults")
+        args = args[:1]
+    return args, kwargs
+
+
 class _Tracer:
     def __init__(self, D, layout):
         self.D, self.dc = int(D), layout == "dc"
@@ -207,54 +306,8 @@ class _Tracer:
         return _E(op, (a, b), a.dep or b.dep)
 
     # -- the graph walk ------------------------------------------------------------------------------------------------
-    def sum_axis_ok(self, dim):
-        if isinstance(dim, (list, tuple)):
-            if len(dim) != 1:
-                return False
-            dim = dim[0]
-        return dim in ((0, -2) if self.dc else (1, -1))
-
     def run(self, fn):
-        import torch.fx as fx
-
-        try:
-            with no_distribution_validation():
-                gm = fx.symbolic_trace(fn)
-        except Exception as e:  # data-dependent control flow, in-place tricks, ...
-            raise Unsupported(f"torch.fx could not trace the function: {type(e).__name__}: {e}") from e
-        table = _function_table()
-        env = {}
-        out = None
-        n_inputs = 0
-        for node in gm.graph.nodes:
-            where = f"node `{node.format_node()}`"
-
-            def val(a):
-                if isinstance(a, (tuple, list)):
-                    return type(a)(val(x) for x in a)
-                return env[a] if isinstance(a, fx.Node) else a
-
-            if node.op == "placeholder":
-                n_inputs += 1
-                if n_inputs > 1:
-                    raise Unsupported("the function takes more than one argument")
-                env[node] = _E("th", (), True)
-            elif node.op == "get_attr":
-                obj = gm
-                for part in node.target.split("."):
-                    obj = getattr(obj, part)
-                env[node] = obj  # (classified where it is used: the operation is what an error should name)
-            elif node.op in ("call_function", "call_method"):
-                name = table.get(node.target) if node.op == "call_function" else _METHODS.get(node.target)
-                if name is None:
-                    raise Unsupported(f"{where}: unsupported operation {getattr(node.target, '__name__', node.target)!r}")
-                args = [val(a) for a in node.args]
-                kwargs = {k: val(v) for k, v in node.kwargs.items()}
-                env[node] = self.apply(name, args, kwargs, where)
-            elif node.op == "output":
-                out = val(node.args[0])
-            else:
-                raise Unsupported(f"{where}: unsupported node kind {node.op}")
+        out = walk(fn, self.apply, _E("th", (), True))
         if not isinstance(out, _Chain):
             raise Unsupported("the function does not end in a per-chain value: it must sum its elementwise expression over "
                               f"the coordinate axis (dim={'0' if self.dc else '1'})")
@@ -273,22 +326,11 @@ class _Tracer:
         raise Unsupported(f"{where}: shape of a value the tracer does not follow")
 
     def apply(self, name, args, kwargs, where):
-        if name == "id":
-            return args[0]
-        if name == "broadcast_tensors":  # (torch.distributions' broadcast_all): the operands themselves; every operation
-            return tuple(args[0]) if len(args) == 1 and isinstance(args[0], (tuple, list)) else tuple(args)  # broadcasts anyway
+        r = plumbing(name, args, where, self.shape_of)
+        if r is not NOT_PLUMBING:
+            return r
         if name == "getitem":
-            src, idx = args
-            if isinstance(src, (tuple, list)) and isinstance(idx, int):
-                return src[idx]
             raise Unsupported(f"{where}: unsupported operation 'getitem' (indexing theta couples coordinates: not elementwise)")
-        if name == "getattr":
-            if args[1] == "shape":
-                return self.shape_of(args[0], where)
-            raise Unsupported(f"{where}: attribute {args[1]!r}")
-        if name == "size":
-            shp = self.shape_of(args[0], where)
-            return shp if len(args) == 1 else shp[args[1]]
         if name in ("reciprocal", "rsqrt"):
             if len(args) != 1 or kwargs:
                 raise Unsupported(f"{where}: {name} with extra arguments")
@@ -299,28 +341,18 @@ class _Tracer:
             return self.chain_op("div", [s, float(self.D)], where)
         if name == "sum":
             x = args[0]
-            dim = args[1] if len(args) > 1 else kwargs.get("dim", kwargs.get("axis"))
-            if kwargs.get("keepdim", False) or (len(args) > 2 and args[2]):
+            dim, keepdim, dtype = sum_args(args, kwargs)
+            if keepdim:
                 raise Unsupported(f"{where}: sum(keepdim=True)")
-            if kwargs.get("dtype") not in (None, torch.float64):
+            if dtype:
                 raise Unsupported(f"{where}: sum(dtype=...)")
             if not isinstance(x, _E) or not x.dep:
                 raise Unsupported(f"{where}: sum of something that is not an elementwise expression of theta")
-            if dim is None or not self.sum_axis_ok(dim):
+            if one_axis(dim) not in ((0, -2) if self.dc else (1, -1)):
                 raise Unsupported(f"{where}: the sum must run over the coordinate axis only "
                                   f"(dim={'0' if self.dc else '1'}), got dim={dim!r}")
             return _Chain(x, 0.0)
-        if name == "relu" and kwargs.get("inplace") is False:
-            kwargs = {}
-        if kwargs and not (name == "softplus" and set(kwargs) <= {"beta", "threshold"}) \
-                and not (name.startswith("clamp") and set(kwargs) <= {"min", "max"}):
-            raise Unsupported(f"{where}: keyword arguments {sorted(kwargs)}")
-        if name == "softplus":
-            beta = kwargs.get("beta", args[1] if len(args) > 1 else 1.0)
-            thr = kwargs.get("threshold", args[2] if len(args) > 2 else 20.0)
-            if float(beta) != 1.0 or float(thr) != 20.0:
-                raise Unsupported(f"{where}: softplus with beta / threshold other than the defaults")
-            args = args[:1]
+        args, kwargs = normalise(name, args, kwargs, where)
         rw = piecewise_rewrite(name, args, kwargs, where)
         if rw is not None:
             return expand_rewrite(rw, lambda n, a: self.apply(n, a, {}, where))

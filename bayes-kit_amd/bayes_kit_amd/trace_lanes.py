@@ -18,13 +18,17 @@ The function is read once with ``torch.fx`` into a hash-consed expression DAG, d
 and emitted as the ``bk_lanes_density`` source of ``csrc/bk_lanes.hpp``'s lane context (``c.head``, ``c.sum``, ``c.grad_head``,
 ``c.grad``): per-chain subexpressions are hoisted out of the row lambdas.  Code generation for ONE backend; anything outside the
 shape raises ``trace.Unsupported`` naming the node.  Only the reference's (C, D) layout.
+
+The DAG (``_Dag``), the traced values (``_Vec`` / ``_Per`` / ``_VecConst``), the operation dispatch (``_DagTracer.apply``), the
+chain-scope generator (``_GenBase``) and the head-gradient bookkeeping (``head_gradients``) are shared with ``trace_chain.py``,
+which imports them from here; ``_LanesTracer`` and ``_Gen`` below hold only what is particular to rows and lambdas.
 """
 from __future__ import annotations
 
 import torch
 
-from .trace import (Unsupported, _function_table, _METHODS, _UNARY, _BINARY, _COMPARE, _HOST_UNARY, TWO_OVER_SQRT_PI, _lit,
-                    no_distribution_validation, piecewise_rewrite, expand_rewrite)
+from .trace import (NOT_PLUMBING, TWO_OVER_SQRT_PI, Unsupported, _BINARY, _COMPARE, _HOST_UNARY, _UNARY, _lit, expand_rewrite,
+                    normalise, one_axis, piecewise_rewrite, plumbing, sum_args, walk)
 
 
 # ---- hash-consed expression DAG ------------------------------------------------------------------------------------------
@@ -276,29 +280,169 @@ _C_BINARY = {"add": "{a} + {b}", "sub": "{a} - {b}", "mul": "{a} * {b}", "div": 
 
 
 # ---- values while walking the fx graph -------------------------------------------------------------------------------------
-class _Row:      # (C, hi - lo): an expression of the row value x, row constants and head-derived per-chain values on rows lo..hi
-    def __init__(self, e, lo, hi):
-        self.e, self.lo, self.hi = e, lo, hi
+class _Vec:      # (C, n): an expression along the coordinate axis; `rows` is the lanes tracer's (lo, hi), the slice it lives on
+    def __init__(self, e, n, rows=None):
+        self.e, self.n, self.rows = e, int(n), rows
 
 
-class _Per:      # (C,) or, broadcast, (C, 1): an expression of heads and sums
+class _Per:      # (C,) or, broadcast, (C, 1): an expression of heads (coordinates taken as scalars) and sums
     def __init__(self, e, bcast=False):
         self.e, self.bcast = e, bcast
 
 
-class _RowConst:  # a tensor constant along the row axis, placed once its partner in an operation says which rows it spans
+class _VecConst:  # a tensor constant along the coordinate axis, placed once its partner in an operation says what it spans
     def __init__(self, t):
         self.t = t
 
 
-class _LanesTracer:
+def _indexed(e):
+    """Does e depend on the position along the coordinate axis (either DAG's leaves)?"""
+    return any(v in ("x", "row") or (isinstance(v, tuple) and v[0] == "x") for v in e.vars)
+
+
+def _full(s):
+    return s is Ellipsis or (isinstance(s, slice) and s == slice(None, None, None))
+
+
+class _DagTracer:
+    """What the lanes tracer (below) and the chain tracer (trace_chain.py) share: the walk's apply() over _Vec / _Per /
+    _VecConst values of a hash-consed DAG `self.g`.  A subclass says what theta is as an operand (theta), what indexing theta
+    or a vector means (index), what a sum over a vector records (reduce), when vectors fit one operation (same_extent), where a
+    tensor constant goes (place), and its own wording (says); FUNCTIONS / METHODS are its extra entries of the walk's tables."""
+    FUNCTIONS = {torch.unsqueeze: "unsqueeze"}
+    METHODS = {"unsqueeze": "unsqueeze"}
+
+    def __init__(self, D, g):
+        self.D, self.g = int(D), g
+        self.TH = object()    # theta itself, until an operation says what it is taken as
+        self.sums = []
+
+    def walk(self, fn):
+        return walk(fn, self.apply, self.TH, self.FUNCTIONS, self.METHODS)
+
+    def operand(self, v, where):
+        """A traced value as an operand of an elementwise operation."""
+        if isinstance(v, (_Vec, _Per, _VecConst)):
+            return v
+        if v is self.TH:
+            return self.theta()
+        if isinstance(v, bool):
+            raise Unsupported(f"{where}: boolean operand")
+        if isinstance(v, (int, float)):
+            return _Per(self.g.const(v), bcast=None)  # scalar: fits both shapes
+        if isinstance(v, torch.Tensor):
+            if v.numel() == 1:
+                return _Per(self.g.const(float(v.reshape(()).item())), bcast=None)
+            return _VecConst(v)
+        raise Unsupported(f"{where}: operand of type {type(v).__name__}")
+
+    def shape_of(self, v, where):
+        if v is self.TH:
+            return (None, self.D)
+        if isinstance(v, _Vec):
+            return (None, v.n)
+        if isinstance(v, _Per):
+            return (None, 1) if v.bcast else (None,)
+        if isinstance(v, torch.Tensor):
+            return tuple(v.shape)
+        raise Unsupported(f"{where}: shape of a value the tracer does not follow")
+
+    def apply(self, name, args, kwargs, where):
+        g, says = self.g, self.says
+        r = plumbing(name, args, where, self.shape_of)
+        if r is not NOT_PLUMBING:
+            return r
+        if name == "getitem":
+            src, idx = args
+            idx = idx if isinstance(idx, tuple) else (idx,)
+            r = self.index(src, idx, where)
+            if r is not None:
+                return r
+            if isinstance(src, _Per) and src.bcast is False and len(idx) == 2 and _full(idx[0]) and idx[1] is None:
+                return _Per(src.e, bcast=True)
+            raise Unsupported(f"{where}: {says['indexing']}")
+        if name == "unsqueeze":
+            src = args[0]
+            dim = args[1] if len(args) > 1 else kwargs.get("dim")
+            if isinstance(src, _Per) and src.bcast is False and dim in (1, -1):
+                return _Per(src.e, bcast=True)
+            raise Unsupported(f"{where}: unsupported unsqueeze")
+        if name == "diff":   # (only the chain tracer's tables hold it)
+            return self.diff(args, kwargs, where)
+        if name in ("sum", "mean"):
+            x = self.theta() if args[0] is self.TH else args[0]
+            dim, keepdim, dtype = sum_args(args, kwargs)
+            dim = one_axis(dim)   # (and the message shows it so: [1] as 1; trace.py's shows dim as written)
+            if keepdim or dtype:
+                raise Unsupported(f"{where}: {name}(keepdim=True) / {name}(dtype=...)")
+            S = self.reduce(x) if isinstance(x, _Vec) else None   # (recorded before the axis is checked: a refusal ends the trace)
+            if S is None:
+                raise Unsupported(f"{where}: {name} of something that is not a {says['vector']}")
+            if dim not in (1, -1):
+                raise Unsupported(f"{where}: the {name} must run over the {says['axis']} (dim=1), got dim={dim!r}")
+            return _Per(S if name == "sum" else g.div(S, g.const(float(x.n))), bcast=False)
+        args, kwargs = normalise(name, args, kwargs, where)
+        if name in ("reciprocal", "rsqrt"):
+            if len(args) != 1:
+                raise Unsupported(f"{where}: {name} with {len(args)} operands")
+            den = args[0] if name == "reciprocal" else self.apply("sqrt", [args[0]], {}, where)
+            return self.apply("div", [1.0, den], {}, where)
+        if name in _UNARY:
+            if len(args) != 1:
+                raise Unsupported(f"{where}: {name} with {len(args)} operands")
+            a = self.operand(args[0], where)
+            if isinstance(a, _VecConst):
+                raise Unsupported(f"{where}: {name} of a tensor constant inside the traced function (compute it outside)")
+            e = g.un(name, a.e)
+            return _Vec(e, a.n, a.rows) if isinstance(a, _Vec) else _Per(e, a.bcast)
+        rw = piecewise_rewrite(name, args, kwargs, where)
+        if rw is not None:
+            return expand_rewrite(rw, lambda n, a: self.apply(n, a, {}, where))
+        if name in _BINARY or name == "where":
+            want = 3 if name == "where" else 2
+            if len(args) != want:
+                raise Unsupported(f"{where}: {name} with {len(args)} operands (alpha= / rounding_mode= are not supported)")
+            ops = [self.operand(v, where) for v in args]
+            if name == "where" and not (isinstance(ops[0], (_Vec, _Per)) and ops[0].e.op in _COMPARE):
+                raise Unsupported(f"{where}: the condition of `where` must be a comparison (> >= < <=)")
+            build = (lambda es: g.where(*es)) if name == "where" else (lambda es: g.bin(name, *es))  # noqa: E731
+            vecs = [o for o in ops if isinstance(o, _Vec)]
+            if vecs:
+                self.same_extent(vecs, where)
+                es = []
+                for o in ops:
+                    if isinstance(o, _VecConst):
+                        es.append(self.place(o.t, vecs[0], where))
+                        continue
+                    if isinstance(o, _Per):
+                        if o.bcast is False:
+                            raise Unsupported(f"{where}: {says['no_bcast']}")
+                        if any(isinstance(v, tuple) and v[0] == "S" for v in o.e.vars):
+                            raise Unsupported(f"{where}: {says['sum_inside']}")
+                    es.append(o.e)
+                return _Vec(build(es), vecs[0].n, vecs[0].rows)
+            if any(isinstance(o, _VecConst) for o in ops):
+                raise Unsupported(f"{where}: {says['stray_const']}")
+            shapes = {o.bcast for o in ops if o.bcast is not None}
+            if len(shapes) > 1:
+                raise Unsupported(f"{where}: a (C,) value meets a (C, 1) value")
+            return _Per(build([o.e for o in ops]), shapes.pop() if shapes else None)
+        raise Unsupported(f"{where}: unsupported operation {name}")
+
+
+class _LanesTracer(_DagTracer):
+    says = {"indexing": "unsupported indexing", "vector": "row expression", "axis": "row axis",
+            "no_bcast": "a per-chain value meets a row expression without [:, None]",
+            "sum_inside": "a sum over the rows is used inside another row expression (rows may depend on head coordinates only)",
+            "stray_const": "a tensor constant meets a per-chain value before any row slice Th[:, a:b]: which rows it "
+                           "spans is unknown (combine it with the rows first)"}
+
     def __init__(self, D):
-        self.D = int(D)
-        self.g = _Dag()
+        super().__init__(D, _Dag())
         self.ranges = set()   # row slices [lo, hi) the function takes
         self.max_head = -1
         self.rows = []        # packed row constants, each (D,) on the host (entries outside their slice unused)
-        self.sums = []        # (e_k, lo, hi)
+        # self.sums: (e_k, lo, hi)
 
     @property
     def H(self):
@@ -306,10 +450,13 @@ class _LanesTracer:
 
     def take_rows(self, lo, hi):
         self.ranges.add((lo, hi))
-        return _Row(self.g.mk("x"), lo, hi)
+        return _Vec(self.g.mk("x"), hi - lo, (lo, hi))
 
-    def row_const(self, t, lo, hi, where):
-        n = hi - lo
+    def theta(self):
+        return self.take_rows(0, self.D)  # the whole state as rows: a density without head coordinates
+
+    def place(self, t, v, where):
+        n, (lo, hi) = v.n, v.rows
         if tuple(t.shape) not in ((n,), (1, n)):
             raise Unsupported(f"{where}: a tensor constant of shape {tuple(t.shape)} does not broadcast along the {n} rows "
                               f"Th[:, {lo}:{hi}] (expected a scalar or shape ({n},) / (1, {n}))")
@@ -322,49 +469,7 @@ class _LanesTracer:
         return self.g.mk("p", len(self.rows) - 1)
 
     def run(self, fn):
-        import torch.fx as fx
-
-        try:
-            with no_distribution_validation():
-                gm = fx.symbolic_trace(fn)
-        except Exception as e:
-            raise Unsupported(f"torch.fx could not trace the function: {type(e).__name__}: {e}") from e
-        table = dict(_function_table())
-        table[torch.unsqueeze] = "unsqueeze"
-        methods = dict(_METHODS, unsqueeze="unsqueeze")
-        env, out, n_inputs = {}, None, 0
-        TH = object()
-        for node in gm.graph.nodes:
-            where = f"node `{node.format_node()}`"
-
-            def val(a):
-                if isinstance(a, fx.Node):
-                    return env[a]
-                if isinstance(a, (tuple, list)):
-                    return type(a)(val(x) for x in a)
-                return a
-
-            if node.op == "placeholder":
-                n_inputs += 1
-                if n_inputs > 1:
-                    raise Unsupported("the function takes more than one argument")
-                env[node] = TH
-            elif node.op == "get_attr":
-                obj = gm
-                for part in node.target.split("."):
-                    obj = getattr(obj, part)
-                env[node] = obj
-            elif node.op in ("call_function", "call_method"):
-                name = table.get(node.target) if node.op == "call_function" else methods.get(node.target)
-                if name is None:
-                    raise Unsupported(f"{where}: unsupported operation {getattr(node.target, '__name__', node.target)!r}")
-                args = [val(a) for a in node.args]
-                kwargs = {k: val(v) for k, v in node.kwargs.items()}
-                env[node] = self.apply(name, args, kwargs, where, TH)
-            elif node.op == "output":
-                out = val(node.args[0])
-            else:
-                raise Unsupported(f"{where}: unsupported node kind {node.op}")
+        out = self.walk(fn)
         if not isinstance(out, _Per) or out.bcast:
             raise Unsupported("the function does not end in a per-chain value built from head coordinates Th[:, i] and sums over "
                               "the rows Th[:, H:]")
@@ -376,177 +481,70 @@ class _LanesTracer:
             raise Unsupported(f"{self.H} head coordinates (the lane-spread kernels hold at most 8)")
         return out.e
 
-    def operand(self, v, where, TH):
-        """A traced value as an operand of an elementwise operation."""
-        if isinstance(v, (_Row, _Per, _RowConst)):
-            return v
-        if v is TH:
-            return self.take_rows(0, self.D)  # the whole state as rows: a density without head coordinates
-        if isinstance(v, bool):
-            raise Unsupported(f"{where}: boolean operand")
-        if isinstance(v, (int, float)):
-            return _Per(self.g.const(v), bcast=None)  # scalar: fits both shapes
-        if isinstance(v, torch.Tensor):
-            if v.numel() == 1:
-                return _Per(self.g.const(float(v.reshape(()).item())), bcast=None)
-            return _RowConst(v)
-        raise Unsupported(f"{where}: operand of type {type(v).__name__}")
+    def index(self, src, idx, where):
+        if src is not self.TH:
+            return None
+        if len(idx) == 2 and _full(idx[0]) and isinstance(idx[1], int) and not isinstance(idx[1], bool) and idx[1] >= 0:
+            self.max_head = max(self.max_head, idx[1])
+            return _Per(self.g.mk("h", idx[1]), bcast=False)
+        if len(idx) == 2 and _full(idx[0]) and isinstance(idx[1], slice) and idx[1].step in (None, 1):
+            lo, hi = idx[1].start, idx[1].stop
+            lo = 0 if lo is None else lo
+            hi = self.D if hi is None else (hi + self.D if isinstance(hi, int) and hi < 0 else hi)
+            if isinstance(lo, int) and isinstance(hi, int) and 0 <= lo < hi <= self.D:
+                return self.take_rows(lo, hi)
+        raise Unsupported(f"{where}: theta may be indexed as Th[:, i] (a head coordinate) or Th[:, a:b] (rows) only")
 
-    def shape_of(self, v, where, TH):
-        if v is TH:
-            return (None, self.D)
-        if isinstance(v, _Row):
-            return (None, v.hi - v.lo)
-        if isinstance(v, _Per):
-            return (None, 1) if v.bcast else (None,)
-        if isinstance(v, torch.Tensor):
-            return tuple(v.shape)
-        raise Unsupported(f"{where}: shape of a value the tracer does not follow")
+    def reduce(self, x):
+        if not _indexed(x.e):
+            return None
+        self.sums.append((x.e, *x.rows))
+        return self.g.mk("S", len(self.sums) - 1)
 
-    def apply(self, name, args, kwargs, where, TH):
-        g = self.g
-        if name == "id":
-            return args[0]
-        if name == "broadcast_tensors":  # (torch.distributions' broadcast_all): the operands themselves; every operation
-            return tuple(args[0]) if len(args) == 1 and isinstance(args[0], (tuple, list)) else tuple(args)  # broadcasts anyway
-        if name == "getattr":
-            if args[1] == "shape":
-                return self.shape_of(args[0], where, TH)
-            raise Unsupported(f"{where}: attribute {args[1]!r}")
-        if name == "size":
-            shp = self.shape_of(args[0], where, TH)
-            return shp if len(args) == 1 else shp[args[1]]
-        if name == "getitem":
-            src, idx = args
-            if isinstance(src, (tuple, list)) and isinstance(idx, int):
-                return src[idx]
-            idx = idx if isinstance(idx, tuple) else (idx,)
-            full = lambda s: s is Ellipsis or (isinstance(s, slice) and s == slice(None, None, None))  # noqa: E731
-            if src is TH:
-                if len(idx) == 2 and full(idx[0]) and isinstance(idx[1], int) and not isinstance(idx[1], bool) and idx[1] >= 0:
-                    self.max_head = max(self.max_head, idx[1])
-                    return _Per(g.mk("h", idx[1]), bcast=False)
-                if len(idx) == 2 and full(idx[0]) and isinstance(idx[1], slice) and idx[1].step in (None, 1):
-                    lo, hi = idx[1].start, idx[1].stop
-                    lo = 0 if lo is None else lo
-                    hi = self.D if hi is None else (hi + self.D if isinstance(hi, int) and hi < 0 else hi)
-                    if isinstance(lo, int) and isinstance(hi, int) and 0 <= lo < hi <= self.D:
-                        return self.take_rows(lo, hi)
-                raise Unsupported(f"{where}: theta may be indexed as Th[:, i] (a head coordinate) or Th[:, a:b] (rows) only")
-            if isinstance(src, _Per) and src.bcast is False and len(idx) == 2 and full(idx[0]) and idx[1] is None:
-                return _Per(src.e, bcast=True)
-            raise Unsupported(f"{where}: unsupported indexing")
-        if name == "unsqueeze":
-            src = args[0]
-            dim = args[1] if len(args) > 1 else kwargs.get("dim")
-            if isinstance(src, _Per) and src.bcast is False and dim in (1, -1):
-                return _Per(src.e, bcast=True)
-            raise Unsupported(f"{where}: unsupported unsqueeze")
-        if name in ("sum", "mean"):
-            x = self.operand(args[0], where, TH) if args[0] is TH else args[0]
-            dim = args[1] if len(args) > 1 else kwargs.get("dim", kwargs.get("axis"))
-            if isinstance(dim, (list, tuple)) and len(dim) == 1:
-                dim = dim[0]
-            if kwargs.get("keepdim", False) or (len(args) > 2 and args[2]) or kwargs.get("dtype") not in (None, torch.float64):
-                raise Unsupported(f"{where}: {name}(keepdim=True) / {name}(dtype=...)")
-            if not isinstance(x, _Row) or "x" not in x.e.vars and "row" not in x.e.vars:
-                raise Unsupported(f"{where}: {name} of something that is not a row expression")
-            if dim not in (1, -1):
-                raise Unsupported(f"{where}: the {name} must run over the row axis (dim=1), got dim={dim!r}")
-            self.sums.append((x.e, x.lo, x.hi))
-            S = g.mk("S", len(self.sums) - 1)
-            return _Per(S if name == "sum" else g.div(S, g.const(float(x.hi - x.lo))), bcast=False)
-        if name == "relu" and kwargs.get("inplace") is False:
-            kwargs = {}
-        if kwargs and not (name == "softplus" and set(kwargs) <= {"beta", "threshold"}) \
-                and not (name.startswith("clamp") and set(kwargs) <= {"min", "max"}):
-            raise Unsupported(f"{where}: keyword arguments {sorted(kwargs)}")
-        if name == "softplus":
-            beta = kwargs.get("beta", args[1] if len(args) > 1 else 1.0)
-            thr = kwargs.get("threshold", args[2] if len(args) > 2 else 20.0)
-            if float(beta) != 1.0 or float(thr) != 20.0:
-                raise Unsupported(f"{where}: softplus with beta / threshold other than the defaults")
-            args = args[:1]
-        if name in ("reciprocal", "rsqrt"):
-            if len(args) != 1:
-                raise Unsupported(f"{where}: {name} with {len(args)} operands")
-            den = args[0] if name == "reciprocal" else self.apply("sqrt", [args[0]], {}, where, TH)
-            return self.apply("div", [1.0, den], {}, where, TH)
-        if name in _UNARY:
-            if len(args) != 1:
-                raise Unsupported(f"{where}: {name} with {len(args)} operands")
-            a = self.operand(args[0], where, TH)
-            if isinstance(a, _RowConst):
-                raise Unsupported(f"{where}: {name} of a tensor constant inside the traced function (compute it outside)")
-            e = g.un(name, a.e)
-            return _Row(e, a.lo, a.hi) if isinstance(a, _Row) else _Per(e, a.bcast)
-        rw = piecewise_rewrite(name, args, kwargs, where)
-        if rw is not None:
-            return expand_rewrite(rw, lambda n, a: self.apply(n, a, {}, where, TH))
-        if name in _BINARY or name == "where":
-            want = 3 if name == "where" else 2
-            if len(args) != want:
-                raise Unsupported(f"{where}: {name} with {len(args)} operands (alpha= / rounding_mode= are not supported)")
-            ops = [self.operand(v, where, TH) for v in args]
-            if name == "where" and not (isinstance(ops[0], (_Row, _Per)) and ops[0].e.op in _COMPARE):
-                raise Unsupported(f"{where}: the condition of `where` must be a comparison (> >= < <=)")
-            build = (lambda es: g.where(*es)) if name == "where" else (lambda es: g.bin(name, *es))  # noqa: E731
-            rows = [o for o in ops if isinstance(o, _Row)]
-            if rows:
-                lo, hi = rows[0].lo, rows[0].hi
-                if any((o.lo, o.hi) != (lo, hi) for o in rows):
-                    raise Unsupported(f"{where}: rows of two different slices in one expression ("
-                                      + " and ".join(sorted({f"Th[:, {o.lo}:{o.hi}]" for o in rows}))
-                                      + "); each expression and its sum must stay within ONE slice")
-                es = []
-                for o in ops:
-                    if isinstance(o, _RowConst):
-                        es.append(self.row_const(o.t, lo, hi, where))
-                        continue
-                    if isinstance(o, _Per):
-                        if o.bcast is False:
-                            raise Unsupported(f"{where}: a per-chain value meets a row expression without [:, None]")
-                        if any(isinstance(v, tuple) and v[0] == "S" for v in o.e.vars):
-                            raise Unsupported(f"{where}: a sum over the rows is used inside another row expression "
-                                              "(rows may depend on head coordinates only)")
-                    es.append(o.e)
-                return _Row(build(es), lo, hi)
-            if any(isinstance(o, _RowConst) for o in ops):
-                raise Unsupported(f"{where}: a tensor constant meets a per-chain value before any row slice Th[:, a:b]: which rows it "
-                                  "spans is unknown (combine it with the rows first)")
-            shapes = {o.bcast for o in ops if o.bcast is not None}
-            if len(shapes) > 1:
-                raise Unsupported(f"{where}: a (C,) value meets a (C, 1) value")
-            return _Per(build([o.e for o in ops]), shapes.pop() if shapes else None)
-        raise Unsupported(f"{where}: unsupported operation {name}")
+    def same_extent(self, vecs, where):
+        if any(o.rows != vecs[0].rows for o in vecs):
+            raise Unsupported(f"{where}: rows of two different slices in one expression ("
+                              + " and ".join(sorted({f"Th[:, {o.rows[0]}:{o.rows[1]}]" for o in vecs}))
+                              + "); each expression and its sum must stay within ONE slice")
 
 
 # ---- code generation: chain scope + row lambdas ----------------------------------------------------------------------------
-class _Gen:
-    def __init__(self, D, H):
-        self.D, self.H = D, H
+class _GenBase:
+    """The chain scope of a generated function (both DAG tracers'): numbered temporaries, a node's C expression, and the
+    emission of a position-independent subtree -- once, under its name."""
+
+    def __init__(self):
         self.outer = []          # lines of the chain scope, in order
         self.names = {}          # node id -> name in the chain scope
         self.n = 0
 
-    def tmp(self, lines, expr):
+    def tmp(self, lines, expr, indent="  "):
         name = f"t{self.n}"
         self.n += 1
-        lines.append(f"  const double {name} = {expr};")
+        lines.append(f"{indent}const double {name} = {expr};")
         return name
 
-    @staticmethod
-    def row_level(e):
-        return "x" in e.vars or "row" in e.vars
+    def head(self, i):
+        """The first use of head i in the chain scope."""
+
+    def expr(self, e, a):
+        if e.op == "sel":
+            return self.sel(e, a)
+        if e.op == "where":
+            return f"({a[0]} != 0.0) ? {a[1]} : {a[2]}"
+        if e.op in _C_UNARY:
+            return _C_UNARY[e.op].format(a=a[0])
+        return _C_BINARY[e.op].format(a=a[0], b=a[1])
 
     def chain(self, e):
-        """Emit e (no row dependency) in the chain scope; returns its name / literal."""
+        """Emit e (no dependency on the position) in the chain scope; returns its name / literal."""
         if e.id in self.names:
             return self.names[e.id]
         if e.op == "c":
             return _lit(e.args[0])
         if e.op == "h":
             r = f"h{e.args[0]}"
+            self.head(e.args[0])
         elif e.op == "S":
             r = f"S{e.args[0]}"
         else:
@@ -554,9 +552,51 @@ class _Gen:
         self.names[e.id] = r
         return r
 
+
+def head_gradients(g, F, sums, heads, wanted, extra_sum):
+    """The chain rule through the sums for the coordinates taken as scalars (heads):
+
+        d log p / d h_i = F_{h_i} + sum_k F_{S_k} * T_{k,i},      T_{k,i} = sum over the positions of d e_k / d h_i
+
+    for sums = [(e_k, n_k)].  A derivative that does not depend on the position is n_k copies of itself; every other T is a
+    sum of its own, the node ('S', K + its number), which extra_sum(k, i, derivative, node) emits.  Returns
+    ([F_{S_k}], {i: d log p / d h_i for i in wanted}, the number of extra sums)."""
+    K, T, extra = len(sums), {}, 0
+    for k, (e, n) in enumerate(sums):
+        for i in heads:
+            de = g.diff(e, ("h", i))
+            if g.is_c(de, 0.0):
+                continue
+            bare = de.args[0] if de.op == "sel" else de
+            if not _indexed(bare):
+                T[(k, i)] = g.mul(g.const(float(n)), bare)
+                continue
+            T[(k, i)] = g.mk("S", K + extra)
+            extra_sum(k, i, de, T[(k, i)])
+            extra += 1
+    FS = [g.diff(F, ("S", k)) for k in range(K)]
+    grads = {}
+    for i in wanted:
+        grads[i] = g.diff(F, ("h", i))
+        for k in range(K):
+            if (k, i) in T:
+                grads[i] = g.add(grads[i], g.mul(FS[k], T[(k, i)]))
+    return FS, grads, extra
+
+
+def _heads_of(F, sums):
+    """The coordinates taken as scalars that F or a summed expression uses, in order."""
+    return sorted({v[1] for e in [F, *sums] for v in e.vars if isinstance(v, tuple) and v[0] == "h"})
+
+
+class _Gen(_GenBase):
+    def __init__(self, D, H):
+        super().__init__()
+        self.D, self.H = D, H
+
     def row(self, e, lines, memo):
         """Emit e inside a row lambda (lines); chain-level subtrees are hoisted into the chain scope and captured."""
-        if not self.row_level(e):
+        if not _indexed(e):
             return self.chain(e)
         if e.id in memo:
             return memo[e.id]
@@ -569,17 +609,11 @@ class _Gen:
         memo[e.id] = r
         return r
 
-    def expr(self, e, a):
-        if e.op == "sel":
-            lo, hi = e.args[1], e.args[2]
-            if (lo, hi) == (self.H, self.D):
-                return a[0]
-            return f"(d >= {lo} && d < {hi}) ? {a[0]} : 0.0"
-        if e.op == "where":
-            return f"({a[0]} != 0.0) ? {a[1]} : {a[2]}"
-        if e.op in _C_UNARY:
-            return _C_UNARY[e.op].format(a=a[0])
-        return _C_BINARY[e.op].format(a=a[0], b=a[1])
+    def sel(self, e, a):
+        lo, hi = e.args[1], e.args[2]
+        if (lo, hi) == (self.H, self.D):
+            return a[0]
+        return f"(d >= {lo} && d < {hi}) ? {a[0]} : 0.0"
 
     def lam(self, e):
         """`[=](double x, i64 d) { ...; return r; }` computing the row expression e."""
@@ -599,39 +633,22 @@ def lanes_source(fn, dims: int):
     if D - H < 1:
         raise Unsupported("no rows beyond the head coordinates")
     sums = [g.sel(e, lo, hi) for e, lo, hi in tr.sums]  # each sum runs over ITS slice: zero on the other rows
-    heads = sorted({v[1] for v in F.vars if isinstance(v, tuple) and v[0] == "h"}
-                   | {v[1] for e in sums for v in e.vars if isinstance(v, tuple) and v[0] == "h"})
     gen = _Gen(D, H)
-    out = []
     for i in range(H):
         gen.outer.append(f"  const double h{i} = c.head({i});")
     # the sums, then the extra sums T[k][i] = sum_d d e_k / d h_i
     for k, e in enumerate(sums):
         lam = gen.lam(e)
         gen.outer.append(f"  const double S{k} = c.sum({lam});")
-    T = {}
-    for k, e in enumerate(sums):
-        for i in heads:
-            de = g.diff(e, ("h", i))
-            if g.is_c(de, 0.0):
-                continue
-            if de.op == "sel" and not _Gen.row_level(de.args[0]):
-                # a row-independent derivative summed over the slice: (hi - lo) copies of it
-                T[(k, i)] = g.mul(g.const(float(de.args[2] - de.args[1])), de.args[0])
-                continue
-            lam = gen.lam(de)
-            gen.outer.append(f"  const double T{k}_{i} = c.sum({lam});")
-            node = g.mk("S", K + len([t for t in T.values() if t.op == "S"]))
-            gen.names[node.id] = f"T{k}_{i}"
-            T[(k, i)] = node
-    FS = [g.diff(F, ("S", k)) for k in range(K)]
-    # d log p / d h_i
+
+    def extra_sum(k, i, de, node):
+        gen.outer.append(f"  const double T{k}_{i} = c.sum({gen.lam(de)});")
+        gen.names[node.id] = f"T{k}_{i}"
+
+    FS, gh, n_extra = head_gradients(g, F, [(e, hi - lo) for e, (_, lo, hi) in zip(sums, tr.sums)], _heads_of(F, sums), range(H),
+                                     extra_sum)
     for i in range(H):
-        gh = g.diff(F, ("h", i))
-        for k in range(K):
-            if (k, i) in T:
-                gh = g.add(gh, g.mul(FS[k], T[(k, i)]))
-        gen.outer.append(f"  c.grad_head({i}, {gen.chain(gh)});")
+        gen.outer.append(f"  c.grad_head({i}, {gen.chain(gh[i])});")
     # d log p / d theta_d
     gx = g.const(0.0)
     for k, e in enumerate(sums):
@@ -643,8 +660,7 @@ def lanes_source(fn, dims: int):
     gen.outer.append(f"  c.grad({lam});")
     gen.outer.append(f"  return {val};")
     src = ("// generated by bayes_kit_amd.trace_lanes from a PyTorch log density (torch.fx graph, symbolic derivatives):\n"
-           f"// {H} head coordinate(s), {K} sum(s) over the rows, {len([t for t in T.values() if t.op == 'S'])} derivative sum(s)\n"
+           f"// {H} head coordinate(s), {K} sum(s) over the rows, {n_extra} derivative sum(s)\n"
            "template <class L>\n__device__ double bk_lanes_density(L& c, const double* P) {\n" + "\n".join(gen.outer) + "\n}\n")
     params = torch.cat(tr.rows) if tr.rows else None
-    return src, H, params, {"head": H, "sums": K, "derivative_sums": len([t for t in T.values() if t.op == "S"]),
-                            "param_rows": len(tr.rows), "temporaries": gen.n}
+    return src, H, params, {"head": H, "sums": K, "derivative_sums": n_extra, "param_rows": len(tr.rows), "temporaries": gen.n}

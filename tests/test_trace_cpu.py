@@ -567,3 +567,82 @@ def test_randomised_hierarchical_densities_against_autograd(tmp_path):
         scale = max(1.0, float(np.abs(gr.numpy()).max()))
         np.testing.assert_allclose(lp_c, lp.detach().numpy(), rtol=1e-11, atol=1e-11, err_msg=f"density {k}")
         np.testing.assert_allclose(g_c, gr.numpy(), rtol=1e-9, atol=1e-11 * scale, err_msg=f"density {k}")
+
+
+# ---- the three tracers' output, pinned: tests/golden/trace_sources.json ----------------------------------------------------
+TRACE_PINS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "trace_sources.json")
+DC_LONG = 150   # chain_source's other regime (D > 128: no unrolling, no pacing); only the densities without length-bound constants
+
+
+def _digest(*parts):
+    import hashlib
+    import json
+
+    h = hashlib.sha256()
+    for p in parts:
+        if isinstance(p, torch.Tensor):
+            p = p.numpy().tobytes()
+        elif isinstance(p, dict):
+            p = json.dumps(p, sort_keys=True)
+        h.update(p if isinstance(p, bytes) else str(p).encode())
+        h.update(b"\0")
+    return h.hexdigest()[:16]
+
+
+def _outcome(call):
+    """The digest of everything a tracer returns, or "U:" + the digest of its Unsupported message."""
+    try:
+        return _digest(*call())
+    except trace.Unsupported as e:
+        return "U:" + _digest(str(e))
+
+
+def trace_pins():
+    """{corpus entry: digest}: every density of this file through its tracer (source text, params bytes, info, head count),
+    every (C, D)-layout function through all three tracers (which tracer accepts what, and each refusal's message), and the full
+    message of every entry of the three `*_name_the_reason` lists."""
+    from bayes_kit_amd import trace_chain, trace_lanes
+
+    pins = {}
+    for name, (fn, layout) in DENSITIES.items():
+        pins[f"term/{name}"] = _outcome(lambda: trace.term_source(fn, D, layout))
+    for name, (fn, _) in LANES.items():
+        pins[f"lanes/{name}"] = _outcome(lambda: trace_lanes.lanes_source(fn, DL))
+    for name, fn in CHAINS.items():
+        pins[f"chain/{name}"] = _outcome(lambda: trace_chain.chain_source(fn, DC))
+    for name in ("second_order_random_walk", "mixed_offsets"):
+        pins[f"chain{DC_LONG}/{name}"] = _outcome(lambda: trace_chain.chain_source(CHAINS[name], DC_LONG))
+    tracers = {"term": lambda fn: trace.term_source(fn, DL), "lanes": lambda fn: trace_lanes.lanes_source(fn, DL),
+               "chain": lambda fn: trace_chain.chain_source(fn, DL)}
+    cd = [(f"DENSITIES/{n}", f) for n, (f, layout) in DENSITIES.items() if layout == "cd"] \
+        + [(f"LANES/{n}", f) for n, (f, _) in LANES.items()] + [(f"CHAINS/{n}", f) for n, f in CHAINS.items()]
+    for name, fn in cd:
+        for t, call in tracers.items():
+            pins[f"cross/{name}/{t}"] = _outcome(lambda: call(fn))
+    needles = {"term": (test_unsupported_functions_name_the_reason, lambda fn: trace.term_source(fn, D)),
+               "lanes": (test_lanes_unsupported_shapes_name_the_reason, lambda fn: trace_lanes.lanes_source(fn, DL)),
+               "chain": (test_chain_unsupported_shapes_name_the_reason, lambda fn: trace_chain.chain_source(fn, DC))}
+    for t, (test, call) in needles.items():
+        for k, (fn, _) in enumerate(test.pytestmark[0].args[1]):
+            pins[f"refusal/{t}/{k}"] = _outcome(lambda: call(fn))
+    return pins
+
+
+def test_generated_sources_and_refusals_are_the_pinned_ones():
+    """The tracers' text is an interface: CTarget.from_source keys its cache on it, the GPU suite's prewarm builds libraries
+    from it, chain_source's pacing was tuned on it.  Every generated source (with params, info, head count) and every
+    Unsupported message of this file's corpus equals the committed digest, byte for byte.  torch.distributions' bodies and
+    fx's node formatting belong to torch: under another torch version than the recorded one the comparison says nothing.
+    Regenerate (on purpose only) with tests/golden/make_trace_sources.py."""
+    import json
+
+    want = json.load(open(TRACE_PINS))
+    if want["torch"] != torch.__version__:
+        pytest.skip(f"pinned under torch {want['torch']}, this is {torch.__version__}")
+    got = trace_pins()
+    assert sorted(got) == sorted(want["digests"])
+    wrong = {k: (got[k], want["digests"][k]) for k in got if got[k] != want["digests"][k]}
+    assert not wrong, wrong
+    assert sum(v.startswith("U:") for k, v in got.items() if k.startswith("cross/")) == 42
+    assert not any(v.startswith("U:") for k, v in got.items() if not k.startswith(("cross/", "refusal/")))
+    assert all(v.startswith("U:") for k, v in got.items() if k.startswith("refusal/"))
