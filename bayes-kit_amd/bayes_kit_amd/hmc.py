@@ -81,8 +81,8 @@ class HMCDiag(ManyChainSampler):
         """The reference's arguments (hmc.py:9-17), then the engine's (ManyChainSampler: chains, chain_id0, path, tuning,
         ops) and ``metric_dense`` (extension: a dense velocity covariance, fp64 MFMA GEMMs).  Tuning knobs (none changes a
         result): ``graph`` (replay a draw as one hipGraph; default: small launch-bound shapes), ``prefetch_rng`` (the next
-        draw's randomness on a side stream; default on), ``tune_placement`` (time which allocation plays which role),
-        ``chain_tile`` (chains per Infinity-Cache tile).
+        draw's randomness on a side stream; default on, except that the tile-major loop generates each tile's in line
+        unless True is given explicitly), ``tune_placement`` (time which allocation plays which role), ``chain_tile`` (chains per Infinity-Cache tile).
 
         ``precond_diag`` (extension; exclusive with metric_diag and metric_dense): a length-D vector v of velocity variances,
         ideally the posterior variances -- the proper diagonal preconditioner, ``oracle.samplers.HMCDense`` with M = diag(v)
@@ -169,7 +169,19 @@ class HMCDiag(ManyChainSampler):
         self._fused_zt = self._fused_draw and self._rng_kind == _lib.RNG_PHILOX and self._dim >= 32
         D, C, dev = self._dim, self._C, self._ops.device
         f64 = dict(dtype=torch.float64, device=dev)
-        self._rho_bufs = [None if self._fused_zt else torch.empty((D, C), **f64)]
+        # The tile-major schedule refreshes each tile's momentum into the tile's own workspace (_draw_tile_major): a sampler
+        # that can take it owns no full-width momentum and no full-size generator scratch until a path that needs them
+        # runs (_rho_full: the untiled loop, a ChEES warm-up, L = 0); a replayed hipGraph allocates up front.  An EXPLICIT
+        # prefetch_rng=True is honoured as what it asks for -- the whole next draw's randomness generated ahead at full width
+        # on the side stream, the tiles' first steps reading their columns of it, the schedule before the per-tile refresh --
+        # while the default leaves the choice to the sampler, which on this loop generates in line (33.85 -> 33.25 ms per draw
+        # at 65,536 x 1,024, profiles/cache_tiles.md section 9).
+        self._tile_ahead = prefetch_rng is True and self._batched and not self._use_graph
+        lazy = self._tile_rng and not self._use_graph and not self._tile_ahead
+        self._work_dropped = lazy and self._rng_work is not None
+        if lazy:
+            self._rng_work = None  # (the engine's full-size scratch drew the initial state; _rho_full brings it back)
+        self._rho_bufs = [None if (self._fused_zt or lazy) else torch.empty((D, C), **f64)]
         self._theta_p = torch.empty((D, C), **f64)
         self._grad = torch.empty((D, C), **f64)      # gradient at the current point
         self._grad_p = torch.empty((D, C), **f64)    # gradient along / at the end of the trajectory
@@ -180,8 +192,9 @@ class HMCDiag(ManyChainSampler):
         self._logu_bufs = [torch.empty(C, **f64)]
         self._ret = torch.empty(C, **f64)
         self._mask = torch.empty(C, dtype=torch.uint8, device=dev)
-        # tile-major schedule: the momentum of the tile in flight, [D, T] contiguous (allocated here: never inside a capture)
-        self._rho_tile = torch.empty(D * self._chain_tile, **f64) if self._chain_tile < C else None
+        # tile-major schedule: the momentum of the tile in flight, [D, T] contiguous, and the generator's scratch for its T
+        # chains (_tile_workspace; allocated below: never inside a capture)
+        self._rho_tile, self._tile_work = None, None
         self._accepted = torch.zeros(1, dtype=torch.int32, device=dev)
         if self._fused_draw:
             self._part = torch.empty(12 * C, **f64)    # quarter partials of the three per-chain sums
@@ -215,7 +228,7 @@ class HMCDiag(ManyChainSampler):
                 self._zt_bufs.append(torch.empty_like(self._zt_bufs[0]))
                 self._rho_bufs.append(None)
             else:
-                self._rho_bufs.append(torch.empty((D, C), **f64))
+                self._rho_bufs.append(None if lazy else torch.empty((D, C), **f64))
             self._kin0_bufs.append(torch.empty(C, **f64))
             self._logu_bufs.append(torch.empty(C, **f64))
             self._ahead = LookAhead(dev)
@@ -223,6 +236,8 @@ class HMCDiag(ManyChainSampler):
                 self._snap = [torch.empty_like(self._rng_state) for _ in range(2)]
             else:
                 self._rng_logical = self._rng_state.clone()  # stream position after the last finished draw
+        if self._tile_rng:
+            self._tile_workspace()
         self.placement = None
         if self._wants_placement_tuning(tune_placement) and not self._fused and self._M is None:
             self._tune_placement()
@@ -402,21 +417,25 @@ class HMCDiag(ManyChainSampler):
     def _tune_placement(self):
         """Roles (theta', grad', rho of each slot, grad): see ManyChainSampler._tune_roles."""
         ops, m, eps = self._ops, self._metric_dev, float(self._stepsize)
-        n_rho = len(self._rho_bufs)
+        # (a sampler on the tile-major schedule owns no full-width momentum: the cached gradient, the third full-width
+        # array of its first steps and selects, then stands in as the step's third array)
+        owned = [r for r in self._rho_bufs if r is not None]
+        n_rho = len(owned)
 
         builtin = hasattr(self._model, "bk_eval")  # the library's own gradient op: safe to time as well
 
         def cost(a):
-            tp, gp, rhos = a[0], a[1], a[2:2 + n_rho]
+            tp, gp, rhos = a[0], a[1], a[2:2 + n_rho] or [a[2]]
             ms = sum(self._time_ms(lambda r=r: ops.kick_drift(tp, tp, r, r, gp, m, eps, False, 0.0, True, eps))
-                     for r in rhos) / n_rho
+                     for r in rhos) / len(rhos)
             if builtin:
                 ms += self._time_ms(lambda: self._model.bk_eval(tp, gp, None))
             return ms
 
-        chosen, rep = self._tune_roles([self._theta_p, self._grad_p] + list(self._rho_bufs) + [self._grad], cost)
+        chosen, rep = self._tune_roles([self._thp_raw, self._gp_raw] + owned + [self._grad], cost)
         self._theta_p, self._grad_p = chosen[0], chosen[1]
-        self._rho_bufs = chosen[2:2 + n_rho]
+        placed = iter(chosen[2:2 + n_rho])
+        self._rho_bufs = [None if r is None else next(placed) for r in self._rho_bufs]
         self._grad = chosen[2 + n_rho]
         key = "step_ms" if builtin else "kick_drift_ms"
         self.placement = {key + "_as_allocated": rep["ms_as_allocated"], key + "_chosen": rep["ms_chosen"],
@@ -470,13 +489,19 @@ class HMCDiag(ManyChainSampler):
         return a.view(-1)
 
     def _draw_tile_major(self, th, rho, kin0, logu, g, m, eps, half, L):
-        """The L steps, the finish, the accept test, the blend into the new state and the select into the cached gradient,
-        tile by tile: everything a tile's end needs (rho, theta', the proposal's gradient) is still in the cache when it
-        runs.  Values, chains and stream positions are those of the untiled schedule, bit for bit."""
+        """The momentum refresh, the L steps, the finish, the accept test, the blend into the new state and the select into
+        the cached gradient, tile by tile: a tile's momentum is generated into the tile's own workspace, and everything its
+        end needs (rho, theta', the proposal's gradient) is still in the cache when it runs.  Values, chains and stream
+        positions are those of the untiled schedule, bit for bit.
+
+        rho None (the default): every tile's randomness is generated IN LINE at the tile's start -- the tile it pushes out of
+        the cache is dead by then, while a generator one tile ahead on the side stream slows the resident steps beside it by
+        as much as it hides (profiles/cache_tiles.md, section 9) -- so nothing is ahead between two draws.  rho given (an
+        explicit prefetch_rng=True): the draw's full-width momentum, generated ahead with kin0 and logu; the first step of a
+        tile reads its columns."""
         ops, D, C, T = self._ops, self._dim, self._C, self._chain_tile
         thp_f, gp_f = self._tm_flat("_thp_raw"), self._tm_flat("_gp_raw")
-        if self._rho_tile is None or self._rho_tile.numel() != D * T:
-            self._rho_tile = torch.empty(D * T, dtype=torch.float64, device=ops.device)
+        self._tile_workspace()
         lp0 = self._lp.clone() if self._stat is not None else None  # (warmup: the statistic sees the log density as it was)
         # the accepted chains take their proposal: a blend into a fresh state array, or (a replayed hipGraph needs fixed
         # addresses) a select in place -- _take()'s two forms
@@ -485,10 +510,13 @@ class HMCDiag(ManyChainSampler):
             n, sl = c1 - c0, slice(c0, c1)
             thp_k, gp_k = thp_f[off:off + D * n].view(D, n), gp_f[off:off + D * n].view(D, n)
             rho_k = self._rho_tile[:D * n].view(D, n)
+            if rho is None:
+                self._tile_randomness(rho_k, kin0[sl], logu[sl], m, sl)
             gl = None
             for s in range(L):
-                if s == 0:  # full-width columns in, the tile's own arrays out
-                    ops.kick_drift_ld(th[:, sl], thp_k, rho[:, sl], rho_k, g[:, sl], m, eps, True, -half, True, eps)
+                if s == 0:  # full-width state and gradient columns in, the tile's own arrays out; the momentum in place
+                    ops.kick_drift_ld(th[:, sl], thp_k, rho_k if rho is None else rho[:, sl], rho_k, g[:, sl], m, eps, True,
+                                      -half, True, eps)
                 else:
                     ops.kick_drift(thp_k, thp_k, rho_k, rho_k, gl, m, eps, False, 0.0, True, eps)
                 gl = self._eval_grad(thp_k, gp_k, self._lp_p[sl] if s == L - 1 else None)
@@ -537,6 +565,10 @@ class HMCDiag(ManyChainSampler):
     # The tiled loop keeps its scratch tile-major and finishes each tile while it is resident (_draw_tile_major): that took the
     # 65,536-chain draw from 37.8 to 36.0 ms and 16,384 / 32,768 chains from 9.23 / 18.61 to 9.00 / 18.09; MIN_TILE and the
     # C >= 2 T rule were not measured again (the new schedule only makes a tile cheaper; the ragged cases above were not rerun).
+    # The loop also refreshes each tile's momentum itself, in line at the tile's start, into the tile's [D, T] workspace through a
+    # scratch chunk for T chains (64 MiB each at 8,192 x 1,024, dead before the tile's second step): 33.85 -> 33.25 ms per draw at
+    # 65,536 chains, 8.48 -> 8.31 and 17.11 -> 16.64 at 16,384 / 32,768, and no full-width momentum or full-size scratch
+    # (profiles/cache_tiles.md, section 9).  The footprint rule above still counts the three arrays of the steady-state step.
     LLC_BYTES = 192 << 20
     MIN_TILE = 8192
 
@@ -649,6 +681,32 @@ class HMCDiag(ManyChainSampler):
             self._ahead.reset()
         self._pf_kin_stale = False
 
+    def _rho_full(self, slot):
+        """The full-width momentum of a slot and the full-size generator scratch, which a sampler on the tile-major
+        schedule allocates only here: when a draw leaves that schedule (the untiled loop, a ChEES warm-up, L = 0)."""
+        if self._rho_bufs[slot] is None:
+            self._rho_bufs[slot] = torch.empty((self._dim, self._C), dtype=torch.float64, device=self._ops.device)
+        if self._work_dropped:
+            self._rng_work, self._work_dropped = self._ops.refresh_work(self._C, self._dim), False
+
+    def _tile_workspace(self):
+        """The tile-major schedule's workspace: a tile's [D, T] momentum and the generator's scratch for T chains (None
+        where the generator takes none: _setup's rule)."""
+        D, T, ops = self._dim, self._chain_tile, self._ops
+        if self._rho_tile is None or self._rho_tile.numel() != D * T:
+            self._rho_tile = torch.empty(D * T, dtype=torch.float64, device=ops.device)
+            self._tile_work = ops.refresh_work(T, D) if self._rng_kind == _lib.RNG_PHILOX and D >= 32 else None
+
+    def _tile_randomness(self, rho_k, kin0, logu, m, sl):
+        """Momentum (into the tile's workspace), kinetic energy and accept uniform of the chains `sl` [hmc.py:56, :37, :60].
+        Each chain's normals, then its uniform: its stream order is that of _randomness, whatever the order of the tiles."""
+        ops, state = self._ops, self._rng_state[:, sl]
+        if self._pd is not None:
+            ops.momentum_refresh_precond(self._rng_kind, state, rho_k, self._pd, kin0, self._tile_work)
+        else:
+            ops.momentum_refresh(self._rng_kind, state, None, 0.0, 1.0, rho_k, m, kin0, None, self._tile_work)
+        ops.log_uniform(self._rng_kind, state, logu)
+
     def _randomness(self, slot):
         """Momentum, kinetic energy and accept uniform of one draw [hmc.py:56, :37, :60]."""
         ops = self._ops
@@ -703,6 +761,9 @@ class HMCDiag(ManyChainSampler):
         """Buffers holding this draw's randomness; with prefetch_rng it was generated ahead, and the next draw's generator is
         queued on the side stream, where it hides under this draw's launches."""
         cur = 0
+        if not self._fused_zt:
+            for slot in range(len(self._rho_bufs)):  # (on the current stream, not where the generator runs)
+                self._rho_full(slot)
         if not self._prefetch:
             self._randomness(0)
         else:
@@ -715,6 +776,25 @@ class HMCDiag(ManyChainSampler):
             self._ahead.start_next(self._randomness, None if self._snap is not None else (self._rng_logical, self._rng_state))
         self._zt_slot = cur
         return self._rho_bufs[cur], self._kin0_bufs[cur], self._logu_bufs[cur]
+
+    @property
+    def _tile_rng(self):
+        """Whether this sampler's draws can take the tile-major loop (what does not change from draw to draw)."""
+        return (self._chain_tile < self._C and self._batched and self._M is None and not self._step_hook
+                and not self._fused_draw and not self._lanes_traj and hasattr(self._ops, "kick_drift_ld"))
+
+    def _tile_major_draw(self):
+        """Whether the draw about to run takes the tile-major loop: _draw's own conditions, in its order."""
+        return self._tile_rng and self._chees is None and int(self._steps) >= 1
+
+    def _tile_major_randomness(self):
+        """The tile-major loop's randomness: the kinetic energies and the accept uniforms of all chains in slot 0's vectors,
+        filled tile by tile, and no full-width momentum.  Randomness that a draw on another schedule generated ahead (a
+        ChEES warm-up, L = 0) is dropped and its stream taken back: the tiles generate the same values again."""
+        self._drop_ahead(rewind=True)
+        self._pf_kin_stale = False
+        self._zt_slot = 0
+        return None, self._kin0_bufs[0], self._logu_bufs[0]
 
     def _graph_key(self):
         return (float(self._stepsize), int(self._steps))
@@ -859,7 +939,10 @@ class HMCDiag(ManyChainSampler):
         # momentum + kinetic energy + accept uniform [hmc.py:56, :37, :60]; the uniform is drawn
         # right after the D normals -- the same stream order as the reference, whose uniform is
         # the next value of the stream whatever happens in between
-        rho, kin0, logu = self._current_randomness()
+        # (the tile-major loop generates them tile by tile, into each tile's workspace)
+        tiled = self._tile_major_draw()
+        in_line = tiled and not self._tile_ahead
+        rho, kin0, logu = self._tile_major_randomness() if in_line else self._current_randomness()
         # warmup(adapt_trajectory=True): the trajectory statistic reads the proposal's velocity, so the finish launch stores
         # it (in place) and the paths that keep it on chip or in a tile's scratch are not taken
         chees = self._chees is not None
@@ -917,10 +1000,10 @@ class HMCDiag(ManyChainSampler):
                                                      hmc_first=True)):
             self._grad_calls += L   # [hmc.py:45-50] in one launch: L gradients of the model's density
             g_last = gp_raw
-        elif (self._chain_tile < self._C and not mirror and self._M is None and not self._step_hook
-              and hasattr(ops, "kick_drift_ld") and not chees):
-            # the tiled model-opaque loop: tile-major scratch, each tile finished while it is resident (an ops layer without
-            # the per-pitch entry points keeps the loop below on column slices of [D, C] arrays: the same draws)
+        elif tiled:
+            # the tiled model-opaque loop: tile-major scratch, each tile refreshed, stepped and finished while it is resident
+            # (an ops layer without the per-pitch entry points keeps the loop below on column slices of [D, C] arrays, and
+            # so does a lane-spread model whose one-launch trajectory declines: the same draws)
             self._draw_tile_major(th, rho, kin0, logu, g, m, eps, half, L)
             return
         else:

@@ -858,7 +858,10 @@ int bk_leapfrog_kick_drift_ld(const double* theta_in, int64_t ld_ti, double* the
   bkt::k_kick_drift_ld<H><<<grid, dim3(bkt::KDL_BLOCK), 0, s>>>(theta_in, ld_ti, theta_out, ld_to, rho_in, ld_ri, rho_out, \
                                                                 ld_ro, grad, ldg_d, metric, eps, use_pre, pre, use_kick, \
                                                                 kick, C / 2, D)
+  // (a momentum updated in place is the tile's own, refreshed into the tile's workspace just before: read plain, 52.4
+  // against 53.4 us at 8,192 x 1,024 -- profiles/cache_tiles.md, section 9)
   if (!past) BK_KDL_LAUNCH(0);
+  else if (!out_past && rho_in == rho_out) BK_KDL_LAUNCH(bkt::NT_IN | bkt::RHO_PLAIN);
   else if (!out_past) BK_KDL_LAUNCH(bkt::NT_IN);
   else BK_KDL_LAUNCH(bkt::NT_IN | bkt::NT_OUT);
 #undef BK_KDL_LAUNCH

@@ -4,6 +4,7 @@
 // 64 lanes of a wavefront because the state layout is chain-contiguous.
 #include "bk_common.hpp"
 #include "bk_rng.hpp"
+#include "bk_tile_kernels.hpp"
 #include "bk_welford.hpp"
 #include "ziggurat_tables.inc"
 
@@ -794,13 +795,28 @@ __global__ __launch_bounds__(256) void k_refresh_apply_kin_rows(const double* zt
   }
 }
 
-// launch of k_refresh_apply_kin / _rows
+// The tile-rate shape (bkt::k_refresh_apply_kin_t: 16 chains per workgroup) is for a call whose arrays -- the scratch, the
+// momentum, the location if any -- fit the last-level cache and whose C / 64 workgroups would leave CUs idle: the momentum
+// of one Infinity-Cache tile of the tile-major HMC schedule (8,192 x 1,024: 512 workgroups instead of 128), read where the
+// generator has just left it.  It stores chain pairs, so the chain count and the pitch are even and the arrays 16-byte
+// aligned; every other call keeps the kernels below.  <8, 8> plain: profiles/cache_tiles.md, section 9.
+constexpr i64 RK_CUS = 256;
+static bool refresh_tile_shape(const double* work, const double* loc_in, const double* out, i64 ld, const double* kin_out,
+                               i64 C, i64 D) {
+  return C % 2 == 0 && ld % 2 == 0 && bk_aligned16(out) && bk_aligned16(kin_out) && bk_aligned16(loc_in) &&
+         bk_cdiv(C, 64) < RK_CUS && !bk_streams_past_llc(bk_distinct_arrays({work, out, loc_in}) * C * D);
+}
+
+// launch of k_refresh_apply_kin / _rows / _t
 template <bool BEGIN, bool PD = false>
 static void refresh_apply_kin_launch(const double* work, i64 dp, const double* loc_in, double loc_mul, double scale,
                                      double* out, i64 ld, const double* metric, double* kin_out, i64 C, i64 D,
                                      const DrBegin& b, hipStream_t s) {
   const size_t lds = (size_t)(64 * (dp + 1) + 256) * sizeof(double);
-  if (dp <= 128 && lds <= 65536)
+  if (!BEGIN && refresh_tile_shape(work, loc_in, out, ld, kin_out, C, D))
+    bkt::k_refresh_apply_kin_t<8, 8, 0, PD><<<dim3((unsigned)bk_cdiv(C / 2, 8)), dim3(bkt::RED_BLOCK), 0, s>>>(
+        work, dp, loc_in, loc_mul, scale, out, ld, metric, kin_out, C / 2, D);
+  else if (dp <= 128 && lds <= 65536)
     k_refresh_apply_kin_rows<BEGIN, PD><<<dim3((unsigned)bk_cdiv(C, 64)), dim3(256), lds, s>>>(work, dp, loc_in, loc_mul, scale,
                                                                                           out, ld, metric, kin_out, C, D, b);
   else if (bk_streams_past_llc(bk_distinct_arrays({work, out, loc_in}) * C * D))

@@ -6,9 +6,10 @@
 //   * the in-place step of a resident tile -- kick+drift and the Gaussian gradient-only kernel -- with a cache policy per
 //     ACCESS (bk_mem_policy.hpp), so that the XCDs' L2s keep theta' across the two launches and nothing else;
 //   * the Gaussian log density (+ gradient) and the finish kernel (half kick + kinetic energy) with enough loads in flight
-//     to run at the cache's rate on a tile's few workgroups -- the SAME summation order as k_gauss_logp(_v2) / k_finish(_v2).
-// Every shape is a template argument: the library instantiates the one it launches (bk_integrator.hip, bk_targets.hip),
-// tools/tile_seam_bench.hip instantiates the candidates it was chosen from (profiles/cache_tiles.md, section 6).
+//     to run at the cache's rate on a tile's few workgroups -- the SAME summation order as k_gauss_logp(_v2) / k_finish(_v2);
+//   * the momentum refresh of ONE tile out of the generator's chain-major scratch, in the same row-spread style.
+// Every shape is a template argument: the library instantiates the one it launches (bk_integrator.hip, bk_targets.hip,
+// bk_rng.hip), tools/tile_seam_bench.hip instantiates the candidates it was chosen from (profiles/cache_tiles.md, sections 6, 9).
 #pragma once
 #include "bk_common.hpp"
 #include "bk_mem_policy.hpp"
@@ -21,6 +22,7 @@ typedef double dvec2 __attribute__((ext_vector_type(2)));
 constexpr int NT_IN = 1;    // the full-width inputs (kick+drift), the full-width old value (blend: a, select: dst)
 constexpr int NT_OUT = 2;   // the outputs
 constexpr int NT_TILE = 4;  // the tile-resident operand of blend / select (b, src)
+constexpr int RHO_PLAIN = 8;  // kick+drift with NT_IN: the momentum is the tile's own (refreshed in place, resident) and read plain
 
 template <bool NT, class T>
 __device__ __forceinline__ T gload(const T* p) {
@@ -52,12 +54,12 @@ __global__ __launch_bounds__(KDL_BLOCK) void k_kick_drift_ld(const double* th_in
                                                              const double* grad, i64 ldg, const double* metric, double eps,
                                                              int use_pre, double pre, int use_kick, double kick, i64 C2,
                                                              i64 D) {
-  constexpr bool NI = (HINTS & NT_IN) != 0, NO = (HINTS & NT_OUT) != 0;
+  constexpr bool NI = (HINTS & NT_IN) != 0, NO = (HINTS & NT_OUT) != 0, NR = NI && (HINTS & RHO_PLAIN) == 0;
   const i64 c2 = (i64)blockIdx.x * KDL_BLOCK + threadIdx.x;
   if (c2 >= C2) return;
   for (i64 d = blockIdx.y; d < D; d += gridDim.y) {
     const dvec2 t = gload<NI>(reinterpret_cast<const dvec2*>(th_in + d * ld_ti + 2 * c2));
-    const dvec2 r = gload<NI>(reinterpret_cast<const dvec2*>(rho_in + d * ld_ri + 2 * c2));
+    const dvec2 r = gload<NR>(reinterpret_cast<const dvec2*>(rho_in + d * ld_ri + 2 * c2));
     const dvec2 g = gload<NI>(reinterpret_cast<const dvec2*>(grad + d * ldg + 2 * c2));
     const double m = metric ? metric[d] : 1.0;
     dvec2 rn, tn;
@@ -380,6 +382,107 @@ __global__ __launch_bounds__(RED_BLOCK) void k_finish_t(const double* rho_in, do
     __syncthreads();
   }
   if (!kin_out) return;
+  if (ph == 0) part[w][j] = kin;
+  __syncthreads();
+  if (w == 0 && ph == 0 && on) {
+    dvec2 s = part[0][j];
+#pragma unroll
+    for (int k = 1; k < RED_WAVES; ++k) {
+      s.x = s.x + part[k][j].x;
+      s.y = s.y + part[k][j].y;
+    }
+    s.x = 0.5 * s.x;
+    s.y = 0.5 * s.y;
+    *reinterpret_cast<dvec2*>(kin_out + 2 * c2) = s;
+  }
+}
+
+// ---- the momentum of ONE tile, out of the generator's chain-major scratch ------------------------------------------------
+// out[d][c] = lo + scale * zt[c][d] and kin[c] = 1/2 (((q0 + q1) + q2) + q3): k_refresh_apply_kin of bk_rng.hip, operation
+// for operation -- lo = loc_in * loc_mul or 0.0, the metric forms (none, diagonal, PD: the packed {v, sqrt(v), 1/v}), each
+// quarter of the dimensions summed in increasing d over v * (m * v).  That kernel serves 64 chains per workgroup (a tile of
+// 8,192 chains: 128 workgroups on 256 CUs) and a lane adds its chain's terms between its own loads.  Here, as in the two
+// reductions above, a workgroup serves CP chain pairs and only the addition is sequential: wavefront w brings the
+// [2 CP chains] x [R = U * 64 / CP dims] piece of its quarter in with 2 U independent 8-byte loads per lane (R consecutive
+// doubles of a chain's row per group of lanes), turns it through an LDS tile, lane (j, ph) writes rows ph, ph + PH, ... of
+// pair j (16 bytes per lane, a full line per row at CP = 8) and leaves the rows' terms IN PLACE of the normals it took; the
+// next piece's loads are issued, then the CP lanes with ph = 0 add the terms in row order.
+// HINTS: NT_IN = the scratch is read non-temporally, NT_OUT = the momentum (and loc_in's pitch) side is.
+// Needs an even chain count and pitch and 16-byte aligned out / loc_in / kin_out (the launch rule of bk_rng.hip); any D, ldz.
+template <int CP, int U, int HINTS, bool PD>
+__global__ __launch_bounds__(RED_BLOCK) void k_refresh_apply_kin_t(const double* zt, i64 ldz, const double* loc_in,
+                                                                   double loc_mul, double scale, double* out, i64 ld,
+                                                                   const double* metric, double* kin_out, i64 C2, i64 D) {
+  constexpr bool NI = (HINTS & NT_IN) != 0, NO = (HINTS & NT_OUT) != 0;
+  constexpr int PH = BK_WAVE / CP, R = U * PH, NC = 2 * CP;
+  constexpr int TP = NC + 2;  // doubles per tile row: 16-byte aligned pairs, rows 144 bytes apart at CP = 8 (not 128)
+  static_assert((U & (U - 1)) == 0 && (CP & (CP - 1)) == 0 && CP <= BK_WAVE, "powers of two");
+  __shared__ __attribute__((aligned(16))) double tile[RED_WAVES][R][TP];
+  __shared__ dvec2 part[RED_WAVES][CP];
+  const int lane = threadIdx.x & (BK_WAVE - 1), w = bk_wave_id(), j = lane % CP, ph = lane / CP;
+  const i64 c2 = (i64)blockIdx.x * CP + j, cb = (i64)blockIdx.x * NC, C = 2 * C2;
+  const bool on = c2 < C2;
+  const i64 Dq = (D + RED_WAVES - 1) / RED_WAVES;
+  const i64 dlo = w * Dq, dhi = (dlo + Dq < D) ? dlo + Dq : D;
+  double z[2 * U];
+  auto load = [&](i64 d0) {  // element e = i * 64 + lane of the [NC][R] piece: chain e / R, dimension e % R
+#pragma unroll
+    for (int i = 0; i < 2 * U; ++i) {
+      const int e = i * BK_WAVE + lane;
+      const i64 cc = cb + e / R, d = d0 + e % R;
+      z[i] = (cc < C && d < dhi) ? gload<NI>(zt + cc * ldz + d) : 0.0;
+    }
+  };
+  dvec2 kin = {0.0, 0.0};
+  load(dlo);
+  for (i64 r0 = 0; r0 < Dq; r0 += R) {  // (the same trip count in the four wavefronts: there are barriers inside)
+    const i64 d0 = dlo + r0;
+#pragma unroll
+    for (int i = 0; i < 2 * U; ++i) {
+      const int e = i * BK_WAVE + lane;
+      tile[w][e % R][e / R] = z[i];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int row = u * PH + ph;
+      const i64 d = d0 + row;
+      if (on && d < dhi) {
+        dvec2* cell = reinterpret_cast<dvec2*>(&tile[w][row][2 * j]);
+        const dvec2 zz = *cell;
+        dvec2 lo = {0.0, 0.0};
+        if (loc_in) {
+          const dvec2 l = gload<NO>(reinterpret_cast<const dvec2*>(loc_in + d * ld + 2 * c2));
+          lo.x = l.x * loc_mul;
+          lo.y = l.y * loc_mul;
+        }
+        const double sc = PD ? metric[D + d] : scale;
+        dvec2 v;
+        v.x = lo.x + sc * zz.x;
+        v.y = lo.y + sc * zz.y;
+        gstore<NO>(v, reinterpret_cast<dvec2*>(out + d * ld + 2 * c2));
+        const double m = PD ? metric[2 * D + d] : (metric ? metric[d] : 1.0);
+        const double mx = (PD || metric) ? m * v.x : v.x, my = (PD || metric) ? m * v.y : v.y;
+        dvec2 tm;
+        tm.x = v.x * mx;
+        tm.y = v.y * my;
+        *cell = tm;
+      }
+    }
+    load(d0 + R);
+    __syncthreads();
+    if (ph == 0 && on) {
+      const i64 left = dhi - d0;
+      const int nr = (int)(left < R ? (left < 0 ? 0 : left) : R);
+#pragma unroll 8
+      for (int r = 0; r < nr; ++r) {
+        const dvec2 tm = *reinterpret_cast<const dvec2*>(&tile[w][r][2 * j]);
+        kin.x = kin.x + tm.x;
+        kin.y = kin.y + tm.y;
+      }
+    }
+    __syncthreads();
+  }
   if (ph == 0) part[w][j] = kin;
   __syncthreads();
   if (w == 0 && ph == 0 && on) {

@@ -14,6 +14,11 @@ ks.sort(key=lambda k: k[1])
 side = [k for k in ks if "k_zig_parallel" in k[0] or "k_refresh_apply" in k[0] or "k_log_uniform" in k[0]]
 
 
+def is_step(n):
+    """The in-place pair of a resident tile: the per-access-policy kernels, or the plain ones of older builds."""
+    return any(k in n for k in ("k_kick_drift_tile", "k_gauss_grad_tile", "k_kick_drift_v2", "k_gauss_grad_v2"))
+
+
 def short(n):
     n = n.replace("void ", "").replace("(anonymous namespace)::", "")
     return n.split("(")[0]
@@ -23,7 +28,7 @@ def short(n):
 t0 = ks[0][1] + 0.4 * (ks[-1][2] - ks[0][1])
 groups = {}
 for n, s, e in ks:
-    if s < t0 or not ("k_kick_drift_v2" in n or "k_gauss_grad_v2" in n):
+    if s < t0 or not is_step(n):
         continue
     ov = "alone"
     for sn, ss, se in side:
@@ -45,7 +50,7 @@ busy = sum(e - s for _, s, e in main)
 span = main[-1][2] - main[0][1]
 print(f"MAIN kernels {len(main)}, busy {busy / 1e6:.2f} ms of span {span / 1e6:.2f} ms")
 # gaps between consecutive step kernels (both tile-sized), in launch order
-steps = [k for k in main if "k_kick_drift_v2" in k[0] or "k_gauss_grad_v2" in k[0]]
+steps = [k for k in main if is_step(k[0])]
 gaps = sorted((steps[i + 1][1] - steps[i][2]) / 1e3 for i in range(len(steps) - 1) if steps[i + 1][1] - steps[i][2] < 200e3)
 n = len(gaps)
 print(f"GAPS between step kernels n={n}: median {gaps[n // 2]:.2f} us  mean {sum(gaps) / n:.2f}  p10 {gaps[n // 10]:.2f}  p90 {gaps[9 * n // 10]:.2f}  "

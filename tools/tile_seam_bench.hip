@@ -1,7 +1,10 @@
-// Stand-alone measurement behind profiles/cache_tiles.md, section 6: the launches at the two ENDS of a tile of the tile-major
-// HMC schedule, as the library's own kernel templates (csrc/bk_tile_kernels.hpp) with the candidate shapes and access hints.
-// One visit of a tile = what hmc.py queues, shortened in the middle:
-//   first step (full-width theta, rho, gradient -> the tile's contiguous arrays), a few in-place (gradient, kick+drift) steps,
+// Stand-alone measurement behind profiles/cache_tiles.md, sections 6 and 9: the launches at the two ENDS of a tile of the
+// tile-major HMC schedule, as the library's own kernel templates (csrc/bk_tile_kernels.hpp) with the candidate shapes and
+// access hints.  One visit of a tile = what hmc.py queues, shortened in the middle:
+//   the tile's normals written chain-major (a fill stands in for the generator: it leaves the 64 MiB chunk in the cache as the
+//   generator does), the momentum refresh out of that chunk into the tile's momentum,
+//   first step (full-width theta, gradient, the tile's momentum in place -> the tile's contiguous arrays), a few in-place
+//   (gradient, kick+drift) steps,
 //   gradient-only launch (the yardstick), log density + gradient, finish, blend into the output state, select into the
 //   cached gradient.
 // Every launch under test is bracketed by HIP events; a configuration visits the 8 tiles of a 65,536-chain state `reps` times,
@@ -37,6 +40,47 @@ __global__ __launch_bounds__(256) void k_grad(const double* th, double* g, i64 l
   *reinterpret_cast<dvec2*>(g + d * ld + 2 * c2) = o;
 }
 
+// the library's momentum refresh of every other call (bk_rng.hip: k_refresh_apply_kin, no location, no metric, plain): 64
+// chains per workgroup -- the yardstick of the tile-rate shapes
+__global__ __launch_bounds__(256) void k_refresh64(const double* zt, i64 ldz, double scale, double* out, i64 ld, double* kin_out,
+                                                   i64 C, i64 D) {
+  __shared__ double tile[4][64][17];
+  __shared__ double part[4][64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x / 64;
+  const i64 c0 = (i64)blockIdx.x * 64, c = c0 + lane;
+  const i64 Dq = (D + 3) / 4;
+  const i64 dlo = w * Dq, dhi = (dlo + Dq < D) ? dlo + Dq : D;
+  const int sub = lane >> 4, dl = lane & 15;
+  double kin = 0.0;
+  for (i64 p0 = 0; p0 < Dq; p0 += 16) {
+    const i64 d0 = dlo + p0;
+    double z[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      i64 cc = c0 + 4 * i + sub, d = d0 + dl;
+      z[i] = (cc < C && d < dhi) ? zt[cc * ldz + d] : 0.0;
+    }
+#pragma unroll
+    for (int i = 0; i < 16; ++i) tile[w][4 * i + sub][dl] = z[i];
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      if (c < C && d0 + u < dhi) {
+        double v = 0.0 + scale * tile[w][lane][u];
+        out[(d0 + u) * ld + c] = v;
+        kin = kin + v * v;
+      }
+    }
+    __syncthreads();
+  }
+  part[w][lane] = kin;
+  __syncthreads();
+  if (w != 0 || c >= C) return;
+  double s = part[0][lane];
+  for (int k = 1; k < 4; ++k) s = s + part[k][lane];
+  kin_out[c] = 0.5 * s;
+}
+
 __global__ void k_fill(double* p, i64 n, double v) {
   for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (i64)gridDim.x * blockDim.x)
     p[i] = v + 1e-9 * (double)(i & 1023);
@@ -49,6 +93,7 @@ __global__ void k_mask(uint8_t* m, i64 n) {  // accepts 4 of 5 chains: every (m0
 struct Args {
   double *th, *rho, *g, *out;  // [D][C]: state, generator's momentum, cached gradient, output state
   double *thp, *rk, *gp;       // [D][T]: the tile's proposal, momentum, trajectory gradient
+  double *zt, *kin0;           // [T][D]: the tile's normals, chain-major; [C]: the momentum's kinetic energy
   double *lam, *lp, *kin;
   uint8_t* mask;
   i64 C, T, D, c0;
@@ -57,10 +102,25 @@ struct Args {
 static i64 cdiv(i64 a, i64 b) { return (a + b - 1) / b; }
 
 template <int H>
-static void first_step(const Args& a) {
+static void first_step(const Args& a) {  // the tile's momentum in place (the refresh has just written it)
+  dim3 grid((unsigned)cdiv(a.T / 2, 256), (unsigned)a.D);
+  bkt::k_kick_drift_ld<H><<<grid, 256, 0, a.s>>>(a.th + a.c0, a.C, a.thp, a.T, a.rk, a.T, a.rk, a.T, a.g + a.c0, a.C,
+                                                 nullptr, 0.01, 1, -0.005, 1, 0.01, a.T / 2, a.D);
+}
+template <int H>
+static void first_step_full(const Args& a) {  // the momentum out of a full-width array in HBM: the schedule before section 9
   dim3 grid((unsigned)cdiv(a.T / 2, 256), (unsigned)a.D);
   bkt::k_kick_drift_ld<H><<<grid, 256, 0, a.s>>>(a.th + a.c0, a.C, a.thp, a.T, a.rho + a.c0, a.C, a.rk, a.T, a.g + a.c0, a.C,
                                                  nullptr, 0.01, 1, -0.005, 1, 0.01, a.T / 2, a.D);
+}
+static void normals(const Args& a) { k_fill<<<1024, 256, 0, a.s>>>(a.zt, a.T * a.D, 0.125); }
+template <int CP, int U, int H>
+static void refresh(const Args& a) {
+  bkt::k_refresh_apply_kin_t<CP, U, H, false><<<(unsigned)cdiv(a.T / 2, CP), 256, 0, a.s>>>(
+      a.zt, a.D, nullptr, 0.0, 1.0, a.rk, a.T, nullptr, a.kin0 + a.c0, a.T / 2, a.D);
+}
+static void refresh64(const Args& a) {
+  k_refresh64<<<(unsigned)cdiv(a.T, 64), 256, 0, a.s>>>(a.zt, a.D, 1.0, a.rk, a.T, a.kin0 + a.c0, a.T, a.D);
 }
 static void step(const Args& a) {
   dim3 grid((unsigned)cdiv(a.T / 2, 256), (unsigned)a.D);
@@ -94,10 +154,11 @@ static void select(const Args& a) {
 typedef void (*Fn)(const Args&);
 struct Cfg {
   const char* name;
-  Fn first, logp, finish, blend, select;
+  Fn first, logp, finish, blend, select, refresh;
 };
-constexpr int I = bkt::NT_IN, O = bkt::NT_OUT, B = bkt::NT_TILE;
+constexpr int I = bkt::NT_IN, O = bkt::NT_OUT, B = bkt::NT_TILE, P = bkt::RHO_PLAIN;
 #define BASE_FIRST first_step<I>
+#define BASE_REF refresh<8, 8, 0>
 #define BASE_LOGP logp<8, 8, 0>
 #define BASE_FIN finish<8, 8, 0>
 #define BASE_BLEND blend<I | O>
@@ -105,23 +166,34 @@ constexpr int I = bkt::NT_IN, O = bkt::NT_OUT, B = bkt::NT_TILE;
 // <chain pairs per wavefront, loads in flight per lane, hints>
 static const Cfg CFG[] = {
     {"base (what the library launches): first nt-in | logp <8,8> plain | finish <8,8> plain | blend, select nt full-width, plain tile",
-     BASE_FIRST, BASE_LOGP, BASE_FIN, BASE_BLEND, BASE_SEL},
-    {"first plain", first_step<0>, BASE_LOGP, BASE_FIN, BASE_BLEND, BASE_SEL},
-    {"first nt-in nt-out", first_step<I | O>, BASE_LOGP, BASE_FIN, BASE_BLEND, BASE_SEL},
-    {"logp, finish <4,8>", BASE_FIRST, logp<4, 8, 0>, finish<4, 8, 0>, BASE_BLEND, BASE_SEL},
-    {"logp, finish <8,4>", BASE_FIRST, logp<8, 4, 0>, finish<8, 4, 0>, BASE_BLEND, BASE_SEL},
-    {"logp, finish <8,16>", BASE_FIRST, logp<8, 16, 0>, finish<8, 16, 0>, BASE_BLEND, BASE_SEL},
-    {"logp, finish <16,8>", BASE_FIRST, logp<16, 8, 0>, finish<16, 8, 0>, BASE_BLEND, BASE_SEL},
-    {"logp, finish <16,16>", BASE_FIRST, logp<16, 16, 0>, finish<16, 16, 0>, BASE_BLEND, BASE_SEL},
-    {"logp, finish <32,8>", BASE_FIRST, logp<32, 8, 0>, finish<32, 8, 0>, BASE_BLEND, BASE_SEL},
-    {"logp <8,8> nt stores | finish <8,8> nt loads", BASE_FIRST, logp<8, 8, O>, finish<8, 8, I>, BASE_BLEND, BASE_SEL},
-    {"blend, select all nt", BASE_FIRST, BASE_LOGP, BASE_FIN, blend<I | O | B>, select<I | O | B>},
-    {"blend, select all plain", BASE_FIRST, BASE_LOGP, BASE_FIN, blend<0>, select<0>},
-    {"base again", BASE_FIRST, BASE_LOGP, BASE_FIN, BASE_BLEND, BASE_SEL},
+     BASE_FIRST, BASE_LOGP, BASE_FIN, BASE_BLEND, BASE_SEL, BASE_REF},
+    {"first plain", first_step<0>, BASE_LOGP, BASE_FIN, BASE_BLEND, BASE_SEL, BASE_REF},
+    {"first nt-in nt-out", first_step<I | O>, BASE_LOGP, BASE_FIN, BASE_BLEND, BASE_SEL, BASE_REF},
+    {"logp, finish <4,8>", BASE_FIRST, logp<4, 8, 0>, finish<4, 8, 0>, BASE_BLEND, BASE_SEL, BASE_REF},
+    {"logp, finish <8,4>", BASE_FIRST, logp<8, 4, 0>, finish<8, 4, 0>, BASE_BLEND, BASE_SEL, BASE_REF},
+    {"logp, finish <8,16>", BASE_FIRST, logp<8, 16, 0>, finish<8, 16, 0>, BASE_BLEND, BASE_SEL, BASE_REF},
+    {"logp, finish <16,8>", BASE_FIRST, logp<16, 8, 0>, finish<16, 8, 0>, BASE_BLEND, BASE_SEL, BASE_REF},
+    {"logp, finish <16,16>", BASE_FIRST, logp<16, 16, 0>, finish<16, 16, 0>, BASE_BLEND, BASE_SEL, BASE_REF},
+    {"logp, finish <32,8>", BASE_FIRST, logp<32, 8, 0>, finish<32, 8, 0>, BASE_BLEND, BASE_SEL, BASE_REF},
+    {"logp <8,8> nt stores | finish <8,8> nt loads", BASE_FIRST, logp<8, 8, O>, finish<8, 8, I>, BASE_BLEND, BASE_SEL, BASE_REF},
+    {"blend, select all nt", BASE_FIRST, BASE_LOGP, BASE_FIN, blend<I | O | B>, select<I | O | B>, BASE_REF},
+    {"blend, select all plain", BASE_FIRST, BASE_LOGP, BASE_FIN, blend<0>, select<0>, BASE_REF},
+    // section 9: the momentum refresh <chain pairs per wavefront, rows in flight per lane, hints> and the first step behind it
+    {"refresh as every other call launches it (64 chains per workgroup)", BASE_FIRST, BASE_LOGP, BASE_FIN, BASE_BLEND, BASE_SEL,
+     refresh64},
+    {"refresh <4,8>", BASE_FIRST, BASE_LOGP, BASE_FIN, BASE_BLEND, BASE_SEL, refresh<4, 8, 0>},
+    {"refresh <8,4>", BASE_FIRST, BASE_LOGP, BASE_FIN, BASE_BLEND, BASE_SEL, refresh<8, 4, 0>},
+    {"refresh <16,4>", BASE_FIRST, BASE_LOGP, BASE_FIN, BASE_BLEND, BASE_SEL, refresh<16, 4, 0>},
+    {"refresh <16,8>", BASE_FIRST, BASE_LOGP, BASE_FIN, BASE_BLEND, BASE_SEL, refresh<16, 8, 0>},
+    {"refresh <32,8>", BASE_FIRST, BASE_LOGP, BASE_FIN, BASE_BLEND, BASE_SEL, refresh<32, 8, 0>},
+    {"refresh <8,8> nt scratch loads", BASE_FIRST, BASE_LOGP, BASE_FIN, BASE_BLEND, BASE_SEL, refresh<8, 8, I>},
+    {"first nt-in, the resident momentum plain", first_step<I | P>, BASE_LOGP, BASE_FIN, BASE_BLEND, BASE_SEL, BASE_REF},
+    {"first nt-in, momentum from a full-width array", first_step_full<I>, BASE_LOGP, BASE_FIN, BASE_BLEND, BASE_SEL, BASE_REF},
+    {"base again", BASE_FIRST, BASE_LOGP, BASE_FIN, BASE_BLEND, BASE_SEL, BASE_REF},
 };
 constexpr int NCFG = sizeof(CFG) / sizeof(CFG[0]);
-constexpr int NB = 7;  // bracketed launches per visit
-static const char* WHAT[NB] = {"first", "step(g+kd)", "grad-only", "logp+grad", "finish", "blend", "select"};
+constexpr int NB = 8;  // bracketed launches per visit
+static const char* WHAT[NB] = {"refresh", "first", "step(g+kd)", "grad-only", "logp+grad", "finish", "blend", "select"};
 
 int main(int argc, char** argv) {
   Args a;
@@ -138,6 +210,8 @@ int main(int argc, char** argv) {
     CHECK(hipMalloc(p, n * 8));
     k_fill<<<1024, 256, 0, a.s>>>(*p, n, 0.5);
   }
+  CHECK(hipMalloc(&a.zt, nt * 8));
+  CHECK(hipMalloc(&a.kin0, a.C * 8));
   for (double** p : tile) {
     CHECK(hipMalloc(p, nt * 8));
     k_fill<<<1024, 256, 0, a.s>>>(*p, nt, 0.25);
@@ -166,6 +240,8 @@ int main(int argc, char** argv) {
       for (int t = 0; t < tiles; ++t) {
         if (r == 0) k = 0;
         a.c0 = (i64)t * a.T;
+        normals(a);
+        timed(c.refresh);
         timed(c.first);
         grad_only(a);
         step(a);
